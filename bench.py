@@ -15,10 +15,15 @@ the metric is quoted on):
   c5  configs[4]  solver loop: 50 objective evaluations x 8192 models per step (fp64: the reference has no
                   fp32 path); sharded over the ranks, no collective per evaluation
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--dump-outputs DIR] [--full]
 
 ``--gpus N`` from a plain ``python`` re-executes itself under ``torch.distributed.run`` (one rank per GPU,
 RCCL); launched under torchrun it reads RANK/LOCAL_RANK/WORLD_SIZE as usual.  Rank 0 prints ONE JSON line.
+
+A plain run does what the headline needs: set up, W warm-up steps, K timed steps, the line (with the roofline of the
+timed launches' own hipEvent times).  ``--full`` adds everything else: the CPU baselines and the parity figures against
+the oracle, the rocprofv3 traffic passes, the secondary configurations.  ``--dump-outputs DIR`` writes what the last
+timed step computed to ``DIR/<name>.npy`` (see ``dump_outputs``).
 """
 import argparse
 import hashlib
@@ -617,6 +622,48 @@ def timed_run(w, steps, warmup, sync, after_step=None):
     f_tot, f_n, s_tot, s_n = w.kf.kernel_ms_totals()   # every launch of the timed region
     w.kf.enable_timing(False)
     return elapsed, f_tot / max(f_n, 1), s_tot / max(s_n, 1)
+
+
+DUMP_BUDGET_BYTES = 48 << 20   # --dump-outputs: all files together (float64)
+DUMP_SEED = 20240601           # the fixed sample of models (and, where one model alone is over budget, of steps) written
+
+
+def dump_outputs(w, out_dir, budget=DUMP_BUDGET_BYTES):
+    """``--dump-outputs``: what the last timed step handed its caller, one float64 ``<name>.npy`` per array (``summed_mle``:
+    the step's own return value).  Per-model vectors [B] are written whole; every [B,T,...] array on the same seeded, sorted
+    sample of models (``models.npy`` lists it) sized so that all files stay under ``budget`` bytes -- and, where a single
+    model is over it, on a seeded sample of its steps (``steps.npy``).  The inputs are seeded, so two builds run with the
+    same arguments can be compared file by file.  On the tape paths ``F`` is the kernels' tape, not an output: left out."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v for k, v in w.bufs.items()
+              if not k.startswith("_") and isinstance(v, torch.Tensor) and not (k == "F" and w.bufs.get("_tape"))}
+    arrays["summed_mle"] = w.total
+    big = [k for k, v in arrays.items() if v.dim() > 1]
+    small_bytes = 8 * sum(v.numel() for k, v in arrays.items() if k not in big)
+    per_model = 8 * sum(arrays[k][0].numel() for k in big)
+    room = max(budget - small_bytes, 0)
+    rng = np.random.default_rng(DUMP_SEED)
+    count = min(w.B, room // max(per_model, 1))
+    steps = None
+    if count == 0:           # one model alone is over the budget: a sample of its steps
+        count = 1
+        steps = np.sort(rng.choice(w.T, size=max(1, w.T * room // max(per_model, 1)), replace=False))
+    models = np.sort(rng.choice(w.B, size=count, replace=False))
+    sel = torch.as_tensor(models, device=w.total.device)
+    written = {"models": models.astype(np.float64)}
+    if steps is not None:
+        written["steps"] = steps.astype(np.float64)
+    for k, v in arrays.items():
+        a = v.index_select(0, sel) if k in big else v
+        if steps is not None and k in big:
+            a = a.index_select(1, torch.as_tensor(steps, device=a.device))
+        written[k] = a.detach().to("cpu", torch.float64).numpy()
+    for k, a in written.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {"dir": out_dir, "files": sorted(written), "models": int(count), "bytes": int(sum(a.nbytes for a in written.values()))}
 
 
 def sample_models(B, count):
@@ -1264,7 +1311,7 @@ def compact_line(res, full_path=None):
         if isinstance(out["cpu_baseline"].get("sample"), str):
             out["cpu_baseline"]["sample"] = out["cpu_baseline"]["sample"][:160]
     for k in ("speedup_vs_cpu_baseline", "speedup_vs_cpu_baseline_checker", "loglik_max_rel_err", "models_per_s", "models_per_s_per_gpu",
-              "summed_mle", "rccl_ranks", "dry_run", "allreduce_check"):
+              "summed_mle", "rccl_ranks", "dry_run", "allreduce_check", "dumped_outputs"):
         if k in res:
             out[k] = res[k]
     if "cpu_baseline_checker" in res:
@@ -1319,6 +1366,13 @@ def main():
                     help="c4 / c4s: the writer of the backward tape (mk_set_kernel_variant MK_VARIANT_TAPE_FILTER; default: the library's)")
     ap.add_argument("--dry-run", action="store_true",
                     help="plumbing check without a GPU (gloo): launch, barrier, max-over-ranks, one JSON line with value null")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the CPU baselines and parity figures, the rocprofv3 traffic passes and "
+                         "(default headline, one GPU) the secondary configurations; --no-cpu-baseline / --no-live-traffic / "
+                         "--no-secondary / --only select among them.  Without it the run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64; [B,...] arrays "
+                         "on a fixed seeded sample of models, under 64 MB in all)")
     args = ap.parse_args()
     config_defaulted = args.config is None
     if config_defaulted:
@@ -1366,6 +1420,7 @@ def main():
     w = None
     tape = False
     collectives = 0
+    dumped = None
     if args.dry_run:
         total = torch.zeros(1, dtype=torch.float64, device=dev)
         for _ in range(warmup):
@@ -1396,6 +1451,7 @@ def main():
 
         elapsed, f_avg, s_avg = timed_run(w, steps, warmup, sync, after_step)
         collectives -= warmup if (dist is not None and mode != "solver") else 0
+        dumped = dump_outputs(w, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     el = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     nranks = torch.ones(1, dtype=torch.float64, device=dev)
     per_rank_ms = ar_ms = None
@@ -1462,7 +1518,9 @@ def main():
             res["models_per_s"] = models_per_s
             res["models_per_s_per_gpu"] = models_per_s / world
             res["summed_mle"] = float(total.item())
-            if world == 1 and not args.no_cpu_baseline:
+            if dumped:
+                res["dumped_outputs"] = dumped
+            if args.full and world == 1 and not args.no_cpu_baseline:
                 host = w.host_inputs()
                 gpu_mle = w.bufs["mle"].cpu().numpy()
                 # `cpu_baseline` is the FAIR leg: oracle/kalman_fast.c, what a CPU can do with the same
@@ -1484,12 +1542,12 @@ def main():
         torch.cuda.empty_cache()
     if rank == 0 and not args.dry_run:
         live = None
-        if world == 1 and dist is None and not args.no_live_traffic and args.batch is None and args.T is None:
+        if args.full and world == 1 and dist is None and not args.no_live_traffic and args.batch is None and args.T is None:
             live = live_traffic(args.config, args.packed_sym, projection_path=args.projection_path)  # after the timed region
         res["roofline"] = build_roofline(args.config, N, K, T, B, mode, missing, f_avg, s_avg, args.packed_sym, live=live, tape=tape,
                                          tape_filter=args.tape_filter)
     # ---- the other BASELINE configurations, AFTER the headline's timed region (one GPU, default headline only) ----
-    if (rank == 0 and world == 1 and not args.dry_run and not args.no_secondary and args.config == "c2"
+    if (args.full and rank == 0 and world == 1 and not args.dry_run and not args.no_secondary and args.config == "c2"
             and args.batch is None and args.T is None and not args.packed_sym):
         res["secondary"] = {}
         cpu = not args.no_cpu_baseline

@@ -5,6 +5,7 @@
 #   ROUND=r06 bash scripts/collect_profiles.sh [configs...]        (default: c2 c3 c4 c4s c5 c4fsym; c2sym / c3sym / c4fsym: packed-symmetric records)
 set -u
 ROUND=${ROUND:-r06}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_${ROUND}; mkdir -p $OUT
 CFGS="${@:-c2 c3 c4 c4s c5 c4fsym}"
@@ -37,14 +38,14 @@ for tag in $CFGS; do
   # the bench line of the plain command (with the CPU baselines for the headline configuration), reading the traffic just taken
   mkdir -p profiles/${ROUND}; cp $OUT/pmc_hbm_${tag}.json profiles/${ROUND}/
   extra="--no-cpu-baseline"; [ $tag = c2 ] && extra=""
-  python bench.py --config $cfg $symflag $extra --no-secondary > $OUT/bench_${tag}.json 2> $OUT/bench_${tag}.err
+  python bench.py --full --config $cfg $symflag $extra --no-secondary > $OUT/bench_${tag}.json 2> $OUT/bench_${tag}.err
   echo "== $tag"; cat $OUT/${tag}_kernel_stats.csv | cut -c1-150; tail -c 400 $OUT/bench_${tag}.json | head -c 400; echo
 done
-# the default command as the driver runs it (headline + the secondary configurations), under kernel-trace and plain
+# the full command (headline + the secondary configurations), under kernel-trace and plain
 cd /tmp; rm -rf /tmp/ktd
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ktd -- python $GRAFT_REPO_ROOT/bench.py --no-live-traffic > $OUT/default_bench_under_rocprof.json 2> $OUT/default_kt.err
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ktd -- python "$REPO"/bench.py --full --no-live-traffic > $OUT/default_bench_under_rocprof.json 2> $OUT/default_kt.err
 f=$(ls /tmp/ktd/*/*kernel_stats.csv 2>/dev/null | head -1)
 if [ -n "$f" ]; then head -1 $f > $OUT/default_kernel_stats.csv; grep "mk::" $f >> $OUT/default_kernel_stats.csv; fi
 cd $GRAFT_REPO_ROOT
-python bench.py --transfers > $OUT/bench_default.json 2> $OUT/bench_default.err   # (--transfers: adds the pcie object)
+python bench.py --full --transfers > $OUT/bench_default.json 2> $OUT/bench_default.err   # (--transfers: adds the pcie object)
 echo "== default"; cat $OUT/default_kernel_stats.csv | cut -c1-160

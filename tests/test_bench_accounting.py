@@ -119,3 +119,39 @@ def test_cpu_legs_take_the_cpus_the_process_may_use():
     assert bench.cpu_leg_threads(1) == 1
     assert 1 <= oracle.usable_cpus() <= (os.cpu_count() or 1)
     assert oracle.num_threads() <= oracle.usable_cpus() and oracle.fast_num_threads() <= oracle.usable_cpus()
+
+
+def test_dump_outputs_writes_a_fixed_sample_under_the_budget(tmp_path):
+    """``--dump-outputs``: per-model vectors whole, [B,T,...] arrays on one seeded sample of models, float64, under the budget;
+    the tape (``F`` on the tape paths) and private entries stay out; a model over the budget on its own is cut in steps."""
+    import types
+
+    import torch
+
+    B, T, n = 64, 50, 6
+    g = torch.Generator().manual_seed(3)
+    bufs = {"mle": torch.rand(B, generator=g, dtype=torch.float64), "status": torch.zeros(B, dtype=torch.int32),
+            "S": torch.rand(T, B, n, generator=g, dtype=torch.float64).transpose(0, 1),      # time-major view, as the engine's
+            "Ps": torch.rand(B, T, n, n, generator=g, dtype=torch.float64), "_rs": 7}
+    w = types.SimpleNamespace(bufs=bufs, total=bufs["mle"].sum().reshape(1), B=B, T=T)
+    budget = 8 * (B + B + 1) + 10 * 8 * T * (n + n * n)                                    # room for 10 models
+    info = bench.dump_outputs(w, str(tmp_path / "a"), budget=budget)
+    assert info["models"] == 10 and info["files"] == ["Ps", "S", "mle", "models", "status", "summed_mle"]
+    got = {k: np.load(str(tmp_path / "a" / (k + ".npy"))) for k in info["files"]}
+    assert all(a.dtype == np.float64 for a in got.values())
+    idx = got["models"].astype(np.int64)
+    assert len(np.unique(idx)) == 10 and np.all(np.diff(idx) > 0)
+    np.testing.assert_array_equal(got["S"], bufs["S"].numpy()[idx])
+    np.testing.assert_array_equal(got["Ps"], bufs["Ps"].numpy()[idx])
+    np.testing.assert_array_equal(got["mle"], bufs["mle"].numpy())
+    assert got["summed_mle"].shape == (1,) and info["bytes"] <= budget + 8 * 10
+    again = bench.dump_outputs(w, str(tmp_path / "b"), budget=budget)                     # the same sample every time
+    np.testing.assert_array_equal(np.load(str(tmp_path / "b" / "models.npy")), got["models"])
+    assert again["bytes"] == info["bytes"]
+    bufs["_tape"] = True
+    bufs["F"] = torch.zeros(B, T, 9, dtype=torch.float64)
+    small = bench.dump_outputs(w, str(tmp_path / "c"), budget=8 * (2 * B + 1) + 8 * T * (n + n * n) // 2)
+    assert "F" not in small["files"] and small["models"] == 1 and "steps" in small["files"]
+    steps = np.load(str(tmp_path / "c" / "steps.npy")).astype(np.int64)
+    assert 0 < len(steps) < T
+    assert np.load(str(tmp_path / "c" / "Ps.npy")).shape == (1, len(steps), n, n)

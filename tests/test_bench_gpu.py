@@ -1,4 +1,4 @@
-"""GPU: the bench line as the driver gets it (``python bench.py``), with the non-headline BASELINE configurations attached
+"""GPU: the bench line of ``python bench.py --full``, with the non-headline BASELINE configurations attached
 after the headline's timed region, and throughput FLOORS so that a performance regression of a kernel turns the GPU test
 tier red.  Floors are ~75 % of the slowest value measured over the round's leases, not targets -- except
 where a bar exists (configs[3]: SURVEY 8d's 37.3 k models/s), which IS the floor.
@@ -29,7 +29,7 @@ SECONDARIES = ("c4", "c5", "c4_state_variances", "c4_full_sym", "generic_c2", "g
 def both(tmp_path_factory):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "TORCHELASTIC_RUN_ID")}
     full = str(tmp_path_factory.mktemp("bench") / "full.json")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "10", "--full-record", full],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "10", "--full-record", full],
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=2400)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -246,3 +246,39 @@ def test_secondary_factor_analysis_wide(line, full):
     assert f4["models_per_s"] >= 8000.0, f4          # round 3 (builder-side probe): 26 k models/s
     sub = f4["always_scipy"]
     assert sub["models"] == 256
+
+
+def _plain(args, tmp):
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "TORCHELASTIC_RUN_ID")}
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, cwd=str(tmp), env=env, capture_output=True,
+                         text=True, timeout=600)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+def test_plain_run_times_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """Without ``--full`` the run is the headline alone: exactly ``--steps`` timed steps, ``ms_per_step`` their mean, no CPU
+    legs, no secondaries.  ``--dump-outputs`` writes the last step's outputs (a seeded sample of models): two runs with
+    different step counts write the same arrays, bit for bit."""
+    import numpy as np
+
+    a = _plain(["--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "a")], tmp_path)
+    b = _plain(["--steps", "5", "--warmup", "2", "--dump-outputs", str(tmp_path / "b")], tmp_path)
+    for line, steps in ((a, 3), (b, 5)):
+        assert line["steps"] == steps and line["ms_per_step"] > 0 and line["dtype"] == "f64" and line["higher_is_better"] is True
+        assert abs(line["value"] - 4096 * 1000 * 1e3 / line["ms_per_step"]) < 1e-6 * line["value"]
+        for k in ("secondary", "cpu_baseline", "cpu_baseline_checker", "cpu_baseline_reference_as_shipped"):
+            assert k not in line, k
+        assert "measured in this run" not in json.dumps(line["roofline"])       # no rocprofv3 child passes
+    files = a["dumped_outputs"]["files"]
+    assert files == b["dumped_outputs"]["files"] and {"mle", "S", "Ps", "F", "Pf", "Xp", "Pp", "models"} <= set(files)
+    assert a["dumped_outputs"]["bytes"] < 64 << 20
+    for name in files:
+        x, y = np.load(str(tmp_path / "a" / (name + ".npy"))), np.load(str(tmp_path / "b" / (name + ".npy")))
+        assert x.dtype == np.float64 and np.isfinite(x).all(), name
+        np.testing.assert_array_equal(x, y, err_msg=name)
+    mle = np.load(str(tmp_path / "a" / "mle.npy"))
+    assert mle.shape == (4096,) and a["summed_mle"] == b["summed_mle"]
+    assert np.load(str(tmp_path / "a" / "S.npy")).shape[1:] == (1000, 10)

@@ -374,7 +374,7 @@ def test_ingest_matches_reference_metran(metran):
 
     from metran_amd import ingest
 
-    files = sorted(glob.glob("/root/reference/examples/data/B21B02140*_res.csv"))
+    files = sorted(glob.glob(os.path.join(_refshim.REFERENCE_ROOT, "examples", "data", "B21B02140*_res.csv")))
     assert len(files) == 5
     series = [ingest.read_series_csv(f, name=os.path.basename(f)[:11]) for f in files]
     mt = metran.Metran([s.copy() for s in series], name="B21B0214")
