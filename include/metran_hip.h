@@ -343,6 +343,21 @@ MK_API int mk_alpha_grad(mk_context *ctx, int64_t B, int64_t R, int64_t N, int64
                          const double *d_alpha /* [B,n] */, const double *d_loadings /* [R,N,K] */,
                          double dt, const double *d_gphi, const double *d_gq, double *d_galpha /* [B,n] */);
 
+/* Leave-one-out predictions of every observed cell (the outlier screen of Metran's worked example: mask one observation,
+ * re-smooth, read get_simulation at that cell -- here for all cells at once, parameters held fixed).  For the observed cell
+ * (t, j) de Jong's deletion result on the backward quantities of the sequential filter gives
+ *     d_loo_means[b,t,j] = E[y_tj | every other cell] * scale + offset,   d_loo_vars[b,t,j] = Var[z_j x_t | every other cell] * scale^2
+ * (scale / offset: mk_problem.d_scale / d_offset; the variance is clipped at 0 as in the projection), NaN at a cell that is not
+ * observed (mk_filter_smooth's projection serves those).  [B,T,N], or [T,B,N] with time_major.  Two launches: the recording
+ * forward pass into d_work -- n_instances * T * mk_loo_work_stride(N, K) doubles, filtered records for N + K <= 16, the backward
+ * tape of MK_OUT_TAPE for 16 < N + K <= 63 -- and one backward walk (adjoint_kernel in its LOO mode, resp. smoother_dk_kernel in
+ * its).  prob->warmup is ignored; d_status (may be NULL) receives the filter's MK_FLAG_* bits.  mk_loo_work_stride returns 0 for
+ * a shape that is not served (not specialised, or N + K >= 64); mk_loo then fails with MK_ERR_SHAPE, as it does under the
+ * size-generic kernel family, and with MK_ERR_INVALID for a buffer that is larger than the allocation it points into. */
+MK_API int64_t mk_loo_work_stride(int64_t N, int64_t K);
+MK_API int mk_loo(mk_context *ctx, const mk_problem *prob, double *d_work, int time_major, double *d_loo_means,
+                  double *d_loo_vars, uint32_t *d_status);
+
 /* kalmansmoother for B instances (kalmanfilter.py:403-476).  Reads out->d_F and out->d_Pf
  * (as written by mk_filter); predicted moments are recomputed from them (Phi diagonal), so
  * d_Xp/d_Pp are not read.  Writes d_S, d_Ps (either may be NULL), d_status. */

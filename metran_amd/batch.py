@@ -8,6 +8,7 @@ number comes from the HIP kernels:
     FactorAnalysisBatch      ->  mk_fa_*                     (Metran.get_factors for all models)
     calibrate_batch          ->  mk_loglik_grad / mk_loglik  (Metran.solve for all models in lock-step)
     simulate_smoothed        ->  filter + projecting smoother (get_simulated_means / _variances)
+    loo_predict              ->  leave-one-out predictions of every observation (get_loo_simulation, get_deletion_residuals)
     smooth_state_variances   ->  state means / variances / decomposition
 
 Results of the last filter / smoother run are cached per parameter set, like ``Metran._run_kalman`` does
@@ -143,7 +144,8 @@ class MetranBatch:
     # ------------------------------------------------------------------ cached kernel runs (Metran._run_kalman)
     def _run(self, kind, alpha):
         """kind: "project" (filter + projecting smoother: sim_means/sim_vars in ORIGINAL units), "smoother" (filter +
-        smoother with the state moments), "filter" (filter with the filtered moments).  One cached result per kind,
+        smoother with the state moments), "filter" (filter with the filtered moments), "loo" (leave-one-out predictions
+        loo_means/loo_vars in ORIGINAL units).  One cached result per kind,
         valid for the parameter set it was computed with (metran.py:978-989 keeps one too)."""
         import torch
 
@@ -163,6 +165,9 @@ class MetranBatch:
             out = self.kf.smooth_state_variances(phi, q)
         elif kind == "filter":
             out = self.kf.filter(phi, q, outputs=("F", "Pf"))
+        elif kind == "loo":
+            self.kf.set_scaling(self._std, self._mean)
+            out = self.kf.loo_predict(phi, q)
         else:
             raise ValueError(kind)
         check_status(out["status"], "MetranBatch(%s)" % kind)
@@ -206,6 +211,45 @@ class MetranBatch:
     def get_simulated_variances(self, alpha=None, standardized=False, method="smoother"):
         """``Metran.get_simulated_variances`` (metran.py:797-829)."""
         return self._simulate(alpha, standardized, method)[1]
+
+    # ------------------------------------------------------------------ leave-one-out predictions (outlier screening)
+    def _loo(self, alpha, standardized):
+        out = self._run("loo", alpha)  # original units
+        means, variances = out["loo_means"], out["loo_vars"]
+        if standardized:
+            means = (means - self._mean[:, None, :]) / self._std[:, None, :]
+            variances = variances / (self._std * self._std)[:, None, :]
+        return means, variances
+
+    def get_loo_simulated_means(self, alpha=None, standardized=False):
+        """Leave-one-out means ``[R,T,N]``: at every observed cell the series' value predicted from every OTHER observation
+        of the model -- what ``mask_observations`` of that one cell followed by ``get_simulated_means`` gives there (the
+        outlier screen of Metran's worked example), for all cells at once; parameters held fixed.  NaN where the cell is
+        not observed (``get_simulated_means`` serves those)."""
+        return self._loo(alpha, standardized)[0]
+
+    def get_loo_simulated_variances(self, alpha=None, standardized=False):
+        """Leave-one-out variances ``[R,T,N]`` of the projected state at every observed cell (NaN elsewhere)."""
+        return self._loo(alpha, standardized)[1]
+
+    def get_loo_simulation(self, r, name, alpha=None, ci=0.05, standardized=False):
+        """``get_simulation``'s DataFrame (``mean``, ``lower``, ``upper``) of the leave-one-out predictions of series ``name`` of
+        model ``r``: row t is what ``get_simulation`` returns at t after masking the observation at t alone; NaN rows where
+        the series is not observed."""
+        j = self._series(r, name)
+        means, variances = self._loo(alpha, standardized)
+        L = int(self.batch.lengths[r])
+        sim = self.batch.frame(r, means[r].cpu().numpy()).iloc[:L, j]
+        return self._band(sim, self.batch.frame(r, variances[r].cpu().numpy()).iloc[:L, j] if ci is not None else None, ci)
+
+    def get_deletion_residuals(self, alpha=None):
+        """Deletion residuals ``[R,T,N]``: (y - loo mean) / sqrt(loo variance) at every observed cell, NaN elsewhere -- the
+        same number in standardised and original units.  A large magnitude flags an outlier."""
+        import torch
+
+        means, variances = self._loo(alpha, True)
+        obs = self.kf.obs
+        return torch.where(torch.isfinite(obs), (obs - means) / torch.sqrt(variances), torch.full_like(means, float("nan")))
 
     def _series(self, r, name):
         names = list(self.batch.names[r])

@@ -98,6 +98,7 @@ struct ShapeModule {
     int (*launch_smoother)(const mk::SmootherArgs *, void *);
     int (*launch_adjoint)(const mk::AdjointArgs *, void *);
     int (*launch_sparse)(const mk::SparseArgs *, void *);
+    int (*launch_loo)(const mk::AdjointArgs *, const mk::SmootherArgs *, void *);
 };
 std::vector<ShapeModule> g_modules;
 std::mutex g_modules_mutex;
@@ -147,6 +148,12 @@ hipError_t dispatch_adjoint(int N, int K, const mk::AdjointArgs &a, hipStream_t 
 {
     if (aot_shape(N, K)) return mk::launch_adjoint(N, K, a, s);
     if (const ShapeModule *m = find_module(N, K)) return (hipError_t)m->launch_adjoint(&a, (void *)s);
+    return hipErrorInvalidValue;
+}
+hipError_t dispatch_loo(int N, int K, const mk::AdjointArgs *na, const mk::SmootherArgs *wa, hipStream_t s)
+{
+    if (aot_shape(N, K)) return mk::launch_loo(N, K, na, wa, s);
+    if (const ShapeModule *m = find_module(N, K)) return (hipError_t)m->launch_loo(na, wa, (void *)s);
     return hipErrorInvalidValue;
 }
 // workspace of the generic smoother: grown on demand, stream-ordered reuse (every launch of a context is on its stream)
@@ -207,7 +214,8 @@ MK_API int mk_register_shape_module(const char *path)
     auto ls = (int (*)(const mk::SmootherArgs *, void *))dlsym(h, "mkmod_launch_smoother");
     auto la = (int (*)(const mk::AdjointArgs *, void *))dlsym(h, "mkmod_launch_adjoint");
     auto lsp = (int (*)(const mk::SparseArgs *, void *))dlsym(h, "mkmod_launch_sparse");
-    if (!abi || !shape || !lf || !ls || !la || !lsp) {
+    auto ll = (int (*)(const mk::AdjointArgs *, const mk::SmootherArgs *, void *))dlsym(h, "mkmod_launch_loo");
+    if (!abi || !shape || !lf || !ls || !la || !lsp || !ll) {
         dlclose(h);
         return fail(MK_ERR_INVALID, "%s is not a metran_hip shape module", path);
     }
@@ -227,7 +235,7 @@ MK_API int mk_register_shape_module(const char *path)
             dlclose(h);
             return MK_OK; // already registered
         }
-    g_modules.push_back(ShapeModule{N, K, h, lf, ls, la, lsp});
+    g_modules.push_back(ShapeModule{N, K, h, lf, ls, la, lsp, ll});
     return MK_OK;
 }
 
@@ -1012,6 +1020,7 @@ MK_API int mk_loglik_grad_phases(mk_context *ctx, const mk_problem *p, double *d
     }
     if (!(phases & MK_GRAD_BACKWARD)) return MK_OK;
     mk::AdjointArgs a;
+    memset(&a, 0, sizeof(a));
     a.upd = upd;
     a.us = upd ? us : 0;
     a.B = p->n_instances;
@@ -1037,6 +1046,111 @@ MK_API int mk_loglik_grad_phases(mk_context *ctx, const mk_problem *p, double *d
     MK_HIP(timing_start(ctx, 1));
     MK_HIP(dispatch_adjoint((int)p->N, (int)p->K, a, ctx->stream));
     MK_HIP(timing_stop(ctx, 1)); // reported in the smoother slot of mk_last_kernel_ms / mk_kernel_ms_totals
+    return MK_OK;
+}
+
+// ---- leave-one-out predictions (de Jong's deletion result on the two backward walks) ----
+MK_API int64_t mk_loo_work_stride(int64_t N, int64_t K)
+{
+    if (N < 1 || K < 1 || !specialised(N, K)) return 0;
+    if (N + K <= 16) return mk::record_stride((int)(N + K));
+    return mk_tape_supported(N, K) ? mk::tape_stride_c((int)N, (int)K) : 0;
+}
+
+MK_API int mk_loo(mk_context *ctx, const mk_problem *p, double *d_work, int time_major, double *d_loo_means, double *d_loo_vars,
+                  uint32_t *d_status)
+{
+    MK_CTX(ctx);
+    if (int rc = check_problem(p)) return rc;
+    if (!d_work || !d_loo_means || !d_loo_vars) return fail(MK_ERR_INVALID, "mk_loo: d_work, d_loo_means and d_loo_vars are required");
+    if (!p->d_obs || !p->d_loadings) return fail(MK_ERR_INVALID, "d_obs and d_loadings are required");
+    const int64_t ws = mk_loo_work_stride(p->N, p->K);
+    if (!ws || ctx->variant[MK_VARIANT_KERNEL_FAMILY] == 1)
+        return fail(MK_ERR_SHAPE, "mk_loo serves specialised shapes with N + K <= 63 (ahead-of-time list or a shape module); "
+                                  "N=%lld, K=%lld is not one%s", (long long)p->N, (long long)p->K,
+                    ws ? " in this context (the size-generic kernel family is selected)" : "");
+    const int64_t n = p->N + p->K;
+    // the buffers' sizes: each must end inside the device allocation it starts in (an interior pointer of a pooled allocation
+    // passes whenever the pool's block is large enough -- the check catches a buffer that is too small, not every misuse)
+    const struct { const double *ptr; int64_t doubles; const char *name; } bufs[3] = {
+        {d_work, p->n_instances * p->T * ws, "d_work (n_instances * T * mk_loo_work_stride(N, K) doubles)"},
+        {d_loo_means, p->n_instances * p->T * p->N, "d_loo_means (n_instances * T * N doubles)"},
+        {d_loo_vars, p->n_instances * p->T * p->N, "d_loo_vars (n_instances * T * N doubles)"}};
+    for (const auto &b : bufs) {
+        hipDeviceptr_t base = nullptr;
+        size_t bytes = 0;
+        if (hipMemGetAddressRange(&base, &bytes, (hipDeviceptr_t)b.ptr) != hipSuccess) {
+            (void)hipGetLastError(); // not a hipMalloc allocation: its size cannot be known here
+            continue;
+        }
+        if ((const char *)b.ptr + b.doubles * (int64_t)sizeof(double) > (const char *)base + bytes)
+            return fail(MK_ERR_INVALID, "mk_loo: %s is larger than the device allocation it points into", b.name);
+    }
+    mk_outputs o;
+    memset(&o, 0, sizeof(o));
+    o.d_status = d_status;
+    o.d_F = d_work;
+    o.time_major = time_major;
+    o.record_stride = ws;
+    if (n <= 16) { // the recording forward pass of mk_loglik_grad, then the adjoint walk in its LOO mode
+        o.d_Pf = d_work + n;
+        o.d_sigmas = d_work + n + n * n;
+        o.d_detfs = o.d_sigmas + 1;
+        if (int rc = do_filter(ctx, p, &o)) return rc;
+        mk::AdjointArgs a;
+        memset(&a, 0, sizeof(a));
+        a.B = p->n_instances;
+        a.R = p->n_records;
+        a.T = p->T;
+        a.bs = time_major ? 1 : p->T;
+        a.ts = time_major ? p->n_instances : 1;
+        a.rs = ws;
+        a.obs_bs = p->obs_time_major ? 1 : p->T;
+        a.obs_ts = p->obs_time_major ? p->n_records : 1;
+        a.obs = p->d_obs;
+        a.phi = p->d_phi;
+        a.q = p->d_q;
+        a.loadings = p->d_loadings;
+        a.obsvar = p->d_obsvar;
+        a.x0 = p->d_x0;
+        a.P0 = p->d_P0;
+        a.F = d_work;
+        a.loo_means = d_loo_means;
+        a.loo_vars = d_loo_vars;
+        a.scale = p->d_scale;
+        a.offset = p->d_offset;
+        MK_HIP(timing_start(ctx, 1));
+        MK_HIP(dispatch_loo((int)p->N, (int)p->K, &a, nullptr, ctx->stream));
+        MK_HIP(timing_stop(ctx, 1));
+        return MK_OK;
+    }
+    // wide models: the tape writer of the projection, then the tape walk in its LOO mode
+    o.flags = MK_OUT_TAPE;
+    o.d_sim_means = d_loo_means;
+    o.d_sim_vars = d_loo_vars;
+    if (int rc = do_filter(ctx, p, &o)) return rc;
+    mk::SmootherArgs a;
+    memset(&a, 0, sizeof(a));
+    a.tape = 1;
+    a.obsvar = p->d_obsvar;
+    a.rs = ws;
+    a.R = p->n_records;
+    a.loadings = p->d_loadings;
+    a.scale = p->d_scale;
+    a.offset = p->d_offset;
+    a.sim_means = d_loo_means;
+    a.sim_vars = d_loo_vars;
+    a.B = p->n_instances;
+    a.T = p->T;
+    a.bs = time_major ? 1 : p->T;
+    a.ts = time_major ? p->n_instances : 1;
+    a.phi = p->d_phi;
+    a.q = p->d_q;
+    a.F = d_work;
+    a.status = d_status;
+    MK_HIP(timing_start(ctx, 1));
+    MK_HIP(dispatch_loo((int)p->N, (int)p->K, nullptr, &a, ctx->stream));
+    MK_HIP(timing_stop(ctx, 1));
     return MK_OK;
 }
 

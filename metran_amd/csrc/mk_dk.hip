@@ -55,10 +55,15 @@ typedef __attribute__((address_space(1))) const void global_cvoid_t;
 // Vt[a][N+k] = Pt[a][N+k] - c_a[k] for an unobserved series a and Vt_FF[k'][k] at lane N + k'.  tests/dk_ref.py::dk_smooth_state.
 // More than 32 series (round 5; the tape then comes from the lane-per-state filter, mk_kernels.hip OUT = 4): the same kernel with
 // 64-bit series masks; the row of N alone is 2 n registers, so beyond n = 40 one wavefront per SIMD owns the register file.
-template <int N, int K, bool HASR, bool STATE = false>
+// LOO (mk_loo): LEAVE-ONE-OUT predictions instead of the projection.  At an observed entry the walk already forms beta = kt.r and
+// alpha = kt'N kt with (r, N) as they stand just after the update; de Jong's deletion result is then
+//     E[y_tj | all other cells] = s2 - (s0 - beta)/(s1 + alpha),   Var[z_j x_t | all other cells] = 1/(s1 + alpha) - R_j
+// for any R (HASR is not needed: R_j enters the variance only).  Unobserved cells are NaN and the unobserved pass is skipped.
+template <int N, int K, bool HASR, bool STATE = false, bool LOO = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(N + K <= 40 ? 2 : 1, N + K <= 40 ? 2 : 1))) smoother_dk_kernel(SmootherArgs a)
 {
     static_assert(!(STATE && HASR), "the state outputs are served for R = 0 (Metran's observation variance, metran.py:382-384)");
+    static_assert(!LOO || !(STATE || HASR), "the leave-one-out walk is an instantiation of its own");
     constexpr int n = N + K, SW = tape_side_c(K), RS = STATE ? state_tape_stride_c(N, K) : tape_stride_c(N, K);
     constexpr int XS = tape_xs_c(N, K), SS = tape_ss_c(N, K), SO = tape_so_c(N, K); // tape block addressing (mk_internal.h)
     static_assert(n > 16 && n + 1 <= 64 && K <= 16 && N >= 2, "one model per wavefront: rows 0..n-1 of N and the r row");
@@ -121,7 +126,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(N + K <
             CB[k][m] = c < N ? v : 0.0;
         });
     });
-    [[maybe_unused]] const double rvar = HASR ? a.obsvar[rec * N + js] : 0.0;
+    [[maybe_unused]] const double rvar = HASR ? a.obsvar[rec * N + js] : ((LOO && a.obsvar) ? a.obsvar[rec * N + js] : 0.0);
     const double scale = a.scale ? a.scale[rec * N + js] : 1.0;
     const double offset = a.offset ? a.offset[rec * N + js] : 0.0;
     if constexpr (STATE) { // the loadings of this lane's series wait in LDS (registers are what this kernel is short of)
@@ -346,7 +351,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(N + K <
         // unobserved series and the factors only -- 13.6 of 36 columns at configs[3], x_c as wavefront-uniform LDS reads for
         // ten entries at a time -- does 0.4x the multiply-adds; it ran the kernel at 71 ms against 56: a uniform LDS read per
         // multiply-add costs more than the 22 broadcast multiply-adds it saves.)
-        if (um && !MK_TUNE_SKIP(a, 64)) {
+        if (!LOO && um && !MK_TUNE_SKIP(a, 64)) {
             load_ent(lowbit(um), ea);
             while (true) {
                 unobs_step(ea, eb);
@@ -357,7 +362,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(N + K <
         }
         wave_lds_sync();
         double mean = s2, var = 0.0;              // observed, R = 0: the observation itself, variance 0 (HASR: set in the observed pass)
-        if (unobs) {
+        if constexpr (LOO) mean = var = __builtin_nan(""); // LOO: an observed cell is set in the observed pass, a missing one stays NaN
+        if (!LOO && unobs) {
             double q0 = 0.0, q1 = 0.0;
             double row[N], rowf[SW];
             load_row<N>(tapeb + js * XS, row);
@@ -397,7 +403,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(N + K <
                         const Ent &E = eo[j & 1];
                         const double w = matvec(E);
                         [[maybe_unused]] double beta = 0.0;
-                        if constexpr (HASR) beta = readlane_f64(w, n);
+                        if constexpr (HASR || LOO) beta = readlane_f64(w, n);
                         const double alpha = MK_TUNE_SKIP(a, 32) ? E.xa * w : wave_sum_mfma(E.xa * w);   // its MFMA chain runs under what follows
                         // rows a < n: N[a][j] - w_a.  The r row (lanes >= n): r_j + v/f - beta -- and beta = r . kt IS that row's own w, so
                         // one multiply-add with the row indicator replaces the lane read of beta, a subtraction, an addition and two
@@ -430,6 +436,13 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(N + K <
                             if (js == j) { // (lanes >= N replicate series N-1: the same values to the same address)
                                 mean = s2 - rvar * (E.s0 - beta);
                                 var = rvar * (1.0 - rvar * E.s1) - rvar * rvar * alpha;
+                            }
+                        }
+                        if constexpr (LOO) {
+                            if (js == j) {
+                                const double iD = 1.0 / (E.s1 + alpha);
+                                mean = s2 - (E.s0 - beta) * iD;
+                                var = iD - rvar;
                             }
                         }
                     }
@@ -542,6 +555,26 @@ static hipError_t launch_dk_nk(const SmootherArgs &a, hipStream_t s)
 hipError_t launch_smoother_dk(int N, int K, const SmootherArgs &a, hipStream_t s)
 {
     MK_SHAPES(MK_CASE_DK)
+    return hipErrorNotSupported;
+}
+
+// The leave-one-out walk of the tape (mk_loo): the shapes of launch_dk_nk, the plain tape, R = 0 or not.
+template <int N, int K>
+static hipError_t launch_loo_dk_nk(const SmootherArgs &a, hipStream_t s)
+{
+    if constexpr (N + K > 16 && N + K + 1 <= 64 && K <= 16) {
+        if (a.tape != 1 || a.rs != tape_stride_c(N, K) || !a.sim_means || !a.sim_vars) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((smoother_dk_kernel<N, K, false, false, true>), dim3((unsigned)a.B), dim3(64), 0, s, a);
+        return hipGetLastError();
+    } else {
+        return hipErrorNotSupported;
+    }
+}
+#define MK_CASE_LOO_DK(NN, KK) \
+    if (N == NN && K == KK) return launch_loo_dk_nk<NN, KK>(a, s);
+hipError_t launch_loo_dk(int N, int K, const SmootherArgs &a, hipStream_t s)
+{
+    MK_SHAPES(MK_CASE_LOO_DK)
     return hipErrorNotSupported;
 }
 

@@ -100,6 +100,10 @@ struct AdjointArgs {
     double *gphi, *gq;               // [B,n] gradient of -2 log L w.r.t. diag(Phi), diag(Q)
     const double *upd;               // update tape written by the recording forward pass (FilterArgs.upd), or NULL: recompute
     long us;                         // its stride per (model, step), adjoint_update_stride_c(N, K)
+    // leave-one-out walk (adjoint_kernel<.., LOO = true>, launch_loo): [.,N] per (b,t), same (bs, ts) addressing as the records;
+    // scale / offset [R,N] or NULL as in mk_problem.  Unused by the gradient.
+    double *loo_means, *loo_vars;
+    const double *scale, *offset;
 };
 
 struct SparseArgs { // objective of ONE record (all instances share it), observed steps only
@@ -130,6 +134,9 @@ hipError_t launch_alpha_grad(long B, long R, int N, int K, const double *alpha, 
 hipError_t launch_smoother(int N, int K, const SmootherArgs &a, hipStream_t s);
 hipError_t launch_smoother_wide(int N, int K, const SmootherArgs &a, hipStream_t s); // mk_wide.hip (n > 16)
 hipError_t launch_smoother_dk(int N, int K, const SmootherArgs &a, hipStream_t s);   // mk_dk.hip (a.tape)
+hipError_t launch_loo_dk(int N, int K, const SmootherArgs &a, hipStream_t s);       // mk_dk.hip: leave-one-out walk of the tape
+// leave-one-out predictions (mk_loo): n <= 16 the adjoint walk over filtered records (*narrow), 16 < n <= 63 the tape walk (*wide)
+hipError_t launch_loo(int N, int K, const AdjointArgs *narrow, const SmootherArgs *wide, hipStream_t s);
 int record_stride(int n); // doubles per packed record for state dimension n
 int record_stride_sym(int n); // ... per packed-symmetric record
 int num_shapes();

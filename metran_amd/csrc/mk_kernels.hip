@@ -1778,8 +1778,14 @@ __global__ void __launch_bounds__(256) fill_gaps_kernel(SparseArgs a, int n)
 //   sums per update and the two matrix-vector products are fused DPP broadcast-FMAs.  One model per
 //   16-lane group (n <= 16); wider models keep the finite-difference path.
 //   Checked against central differences of the oracle and a numpy restatement (tests/adjoint_ref.py).
+// LOO = true: the same walk with unit weights on every step (warmup ignored) is a LEAVE-ONE-OUT pass (mk_loo).  There
+//   xb = -2 r and Pb = N - r r' (the Durbin-Koopman quantities just after the update), so de Jong's deletion result for the
+//   observed cell (t, j) reads off the update's own a and c:
+//       D = 1/f + (c + a^2/4)/f^2,   E[y_tj | all other cells] = y_tj - (v + a/2)/(f D),   Var[z_j x_t | ...] = 1/D - R_j
+//   Lane j keeps its series' pair and stores it once a step (NaN where the series is not observed); no gradient sums are formed.
+//   Restated in tests/loo_ref.py.
 // =====================================================================================
-template <int N, int K, int G>
+template <int N, int K, int G, bool LOO = false>
 __global__ void __launch_bounds__(256) adjoint_kernel(AdjointArgs a)
 {
     constexpr int n = N + K;
@@ -1824,7 +1830,7 @@ __global__ void __launch_bounds__(256) adjoint_kernel(AdjointArgs a)
     double ones[n];
 #pragma unroll
     for (int c = 0; c < n; ++c) ones[c] = 1.0;
-    const long sctot = a.sigmacount[inst]; // observed steps in total (written by the forward filter)
+    const long sctot = LOO ? 0 : a.sigmacount[inst]; // observed steps in total (written by the forward filter)
     long rem = 0;                          // observed steps already walked (from the end)
     const double one = 1.0;
 
@@ -1850,6 +1856,22 @@ __global__ void __launch_bounds__(256) adjoint_kernel(AdjointArgs a)
 #pragma unroll
     for (int c = 0; c < n; ++c) Pb[c] = 0.0;
     double xnext, Pnext[n], ynext;
+    // LOO: lane j < N's output cell of the step walked, its scaling, and the pair of its update (the gradient holds none of it)
+    struct LooLane {
+        double *om, *ov;
+        long step;
+        double scale, offset, mean, var;
+    };
+    struct NoLoo {};
+    [[maybe_unused]] typename std::conditional<LOO, LooLane, NoLoo>::type lo;
+    if constexpr (LOO) {
+        const bool own = live && lane < N;
+        lo.om = own ? a.loo_means + (inst * a.bs + (T - 1) * a.ts) * N + lane : nullptr;
+        lo.ov = own ? a.loo_vars + (inst * a.bs + (T - 1) * a.ts) * N + lane : nullptr;
+        lo.step = a.ts * N;
+        lo.scale = a.scale ? a.scale[rec * N + jr] : 1.0;
+        lo.offset = a.offset ? a.offset[rec * N + jr] : 0.0;
+    }
     load_prev(T - 1, xnext, Pnext);
     ynext = obase[(T - 1) * ostep];
 
@@ -1865,8 +1887,9 @@ __global__ void __launch_bounds__(256) adjoint_kernel(AdjointArgs a)
         const unsigned long long ball = __ballot(lane < N && isfinite(y));
         const auto vm = Gp::group_bits(ball);
 
+        if constexpr (LOO) lo.mean = lo.var = __builtin_nan("");
         if (vm != 0) { // uniform within the lane group
-            const double w = (sctot - rem - 1 >= a.warmup) ? 1.0 : 0.0; // compressed index of this step (:563-564)
+            const double w = LOO ? 1.0 : ((sctot - rem - 1 >= a.warmup) ? 1.0 : 0.0); // compressed index of this step (:563-564)
             ++rem;
             // ---- forward: prediction and scalar updates of step t, as filter_kernel ----
             double x = phi_r * xprev, P[n];
@@ -1939,6 +1962,15 @@ __global__ void __launch_bounds__(256) adjoint_kernel(AdjointArgs a)
                         csum = 0.0;
                         sfor<0, n>(MK_LAMBDA(cc) { Gp::template fmac<decltype(cc)::value, false>(csum, ps, one); });
                     }
+                    if constexpr (LOO) { // the deletion pair of this update, from (a, c) as they stand before it is pulled back
+                        const double ha = 0.5 * asum;
+                        const double D = fma(fma(ha, ha, csum) * rf, rf, rf);
+                        const double iD = 1.0 / D;
+                        if (r == j) {
+                            lo.mean = y - (v + ha) * rf * iD;
+                            lo.var = iD - rvar;
+                        }
+                    }
                     const double vrf = v * rf;
                     const double vbar = fma(2.0 * w, v, asum) * rf;
                     const double fbar = (fma(-w * v, vrf, w) - asum * vrf + csum * rf) * rf;
@@ -1958,6 +1990,19 @@ __global__ void __launch_bounds__(256) adjoint_kernel(AdjointArgs a)
                 }
             });
         }
+        if constexpr (LOO) {
+            if (lo.om) {
+                const double sv = lo.scale * lo.scale * lo.var;
+                *lo.om = fma(lo.scale, lo.mean, lo.offset);
+                *lo.ov = sv < 0.0 ? 0.0 : sv; // as the projection (kalmanfilter.py:601-602); NaN stays NaN
+                lo.om -= lo.step;
+                lo.ov -= lo.step;
+            }
+#pragma unroll
+            for (int c = 0; c < n; ++c) Pb[c] *= pp[c];
+            xb *= phi_r;
+            continue;
+        }
         // ---- prediction adjoint ----
         double diag = 0.0, ts0 = 0.0, ts1 = 0.0;
         double phv = phi_r;
@@ -1974,7 +2019,7 @@ __global__ void __launch_bounds__(256) adjoint_kernel(AdjointArgs a)
         gphi = fma(xb, xprev, fma(2.0, ts0 + ts1, gphi));
         xb *= phi_r;
     }
-    if (live && lane < n) {
+    if (!LOO && live && lane < n) {
         if (a.gphi) a.gphi[inst * n + lane] = gphi;
         if (a.gq) a.gq[inst * n + lane] = gq;
     }
@@ -2224,6 +2269,12 @@ MK_API int mkmod_launch_adjoint(const AdjointArgs *a, void *stream)
     get_shape(0, &N, &K);
     return (int)launch_adjoint(N, K, *a, (hipStream_t)stream);
 }
+MK_API int mkmod_launch_loo(const AdjointArgs *narrow, const SmootherArgs *wide, void *stream)
+{
+    int N, K;
+    get_shape(0, &N, &K);
+    return (int)launch_loo(N, K, narrow, wide, (hipStream_t)stream);
+}
 MK_API int mkmod_shape(int *N, int *K)
 {
     get_shape(0, N, K);
@@ -2327,6 +2378,29 @@ static hipError_t launch_adjoint_nk(const AdjointArgs &a, hipStream_t s)
 hipError_t launch_adjoint(int N, int K, const AdjointArgs &a, hipStream_t s)
 {
     MK_SHAPES(MK_CASE_ADJOINT)
+    return hipErrorInvalidValue;
+}
+
+// leave-one-out predictions: the adjoint walk in its LOO mode (n <= 16) or the tape walk of mk_dk.hip (16 < n <= 63)
+template <int N, int K>
+static hipError_t launch_loo_nk(const AdjointArgs *na, const SmootherArgs *wa, hipStream_t s)
+{
+    constexpr int n = N + K;
+    if constexpr (n <= 16) {
+        if (!na || !na->loo_means || !na->loo_vars) return hipErrorInvalidValue;
+        constexpr int GPB = 256 / 16;
+        hipLaunchKernelGGL((adjoint_kernel<N, K, 16, true>), dim3((unsigned)((na->B + GPB - 1) / GPB)), dim3(256), 0, s, *na);
+        return hipGetLastError();
+    } else {
+        if (!wa) return hipErrorInvalidValue;
+        return launch_loo_dk(N, K, *wa, s);
+    }
+}
+#define MK_CASE_LOO(NN, KK) \
+    if (N == NN && K == KK) return launch_loo_nk<NN, KK>(na, wa, s);
+hipError_t launch_loo(int N, int K, const AdjointArgs *na, const SmootherArgs *wa, hipStream_t s)
+{
+    MK_SHAPES(MK_CASE_LOO)
     return hipErrorInvalidValue;
 }
 

@@ -706,6 +706,46 @@ class BatchedKalman:
         check(self._L.mk_filter_smooth(self._ctx, ctypes.byref(prob), ctypes.byref(o)))
         return res
 
+    # ------------------------------------------------------------------ leave-one-out predictions
+    def loo_supported(self):
+        """True when ``loo_predict`` serves this engine's shape (C ABI ``mk_loo_work_stride`` > 0): specialised kernels and
+        N + K <= 63 -- the adjoint walk over filtered records for N + K <= 16, the tape walk above."""
+        return (self.loadings is not None and self.get_variant("kernel_family") == "specialised"
+                and int(self._L.mk_loo_work_stride(self.N, self.K)) > 0)
+
+    def _loo_stride(self):
+        if not self.loo_supported():
+            raise MetranHipError("leave-one-out predictions serve specialised shapes with N + K <= 63; (N=%s, K=%s) is not one"
+                                 % (self.N, getattr(self, "K", None)))
+        return int(self._L.mk_loo_work_stride(self.N, self.K))
+
+    def alloc_loo(self, B):
+        """Buffers of ``loo_predict`` for B instances (the forward pass's workspace + the two outputs), for callers that run
+        it repeatedly (pass them back as ``buffers=``)."""
+        torch = _torch()
+        return {"_work": self._empty_bt(B, self.T, self._loo_stride()),
+                "loo_means": self._empty_bt(B, self.T, self.N), "loo_vars": self._empty_bt(B, self.T, self.N),
+                "status": torch.zeros(B, dtype=torch.int32, device=self.device)}
+
+    def loo_predict(self, phi, q, x0=None, P0=None, buffers=None):
+        """LEAVE-ONE-OUT predictions of every observed cell for B instances (C ABI ``mk_loo``): ``loo_means[b,t,j]`` is the
+        prediction of observation (t, j) from every OTHER observation of the record and ``loo_vars[b,t,j]`` the variance of
+        the projected state z_j x_t under it -- what masking that one cell, smoothing again and reading ``simulate`` at the
+        cell gives (Metran's outlier screen, metran.py:464-506 + 831-883), parameters held fixed -- for all cells in two
+        launches.  Units as set by ``set_scaling`` (scale / offset of the projection); NaN where a cell is not observed.
+        Returns a dict with ``loo_means, loo_vars`` ``[B,T,N]`` and ``status`` (the filter's MK_FLAG_* bits)."""
+        stride = self._loo_stride()
+        prob, keep, B = self._problem(phi, q, 0, x0, P0)
+        res = buffers if buffers is not None else self.alloc_loo(B)
+        for key, tail in (("_work", stride), ("loo_means", self.N), ("loo_vars", self.N)):
+            t = res[key]
+            if tuple(t.shape) != (B, self.T, tail) or self._layout(t) is not t:
+                raise ValueError("buffers[%r] must be a [%d,%d,%d] tensor in the engine's layout (alloc_loo)" % (key, B, self.T, tail))
+        self._bind_stream()
+        check(self._L.mk_loo(self._ctx, ctypes.byref(prob), self._p(res["_work"]), 1 if self.time_major else 0,
+                             self._p(res["loo_means"]), self._p(res["loo_vars"]), self._p(res["status"])))
+        return res
+
     def state_tape_path(self):
         """True when ``smooth_state_variances`` runs over the STATE tape (``MK_OUT_TAPE | MK_OUT_VAR_ONLY``: the tape of
         ``tape_path`` plus K factor entries per step; ``mk_dk.hip`` STATE = true): the shapes of ``tape_path`` with zero
