@@ -849,6 +849,10 @@ static int do_smooth(mk_context *ctx, const mk_problem *p, const mk_outputs *o)
     if ((sym || tape) && (!specialised(p->N, p->K) || ctx->variant[MK_VARIANT_KERNEL_FAMILY] == 1))
         return fail(MK_ERR_SHAPE, "packed-symmetric records and the tape exist for specialised shapes only (N=%lld, K=%lld runs the "
                                   "size-generic kernels: mk_shape_specialised)", (long long)p->N, (long long)p->K);
+    if ((a.variant & 2) && !sym && !var && !tape && p->N + p->K > mk::wave_smoother_max_n && specialised(p->N, p->K) &&
+        ctx->variant[MK_VARIANT_KERNEL_FAMILY] == 0)
+        return fail(MK_ERR_SHAPE, "the round-1 wide smoother (MK_VARIANT_WIDE_SMOOTHER 1) is built for N + K <= %d (got N=%lld, K=%lld)",
+                    mk::wave_smoother_max_n, (long long)p->N, (long long)p->K);
     MK_HIP(dispatch_smoother(ctx, (int)p->N, (int)p->K, a, ctx->stream));
     MK_HIP(timing_stop(ctx, 1));
     return MK_OK;

@@ -21,6 +21,12 @@
 
 namespace mk {
 
+// the round-1 wide smoother (smoother_wave_kernel, mk_wide.hip: the "v1" A/B reference of MK_VARIANT_WIDE_SMOOTHER) is instantiated
+// up to this state dimension only: its fully unrolled n-wide register arrays spill beyond it, and hipcc's time on the kernel
+// grows steeply (slice 0 of mk_wide.hip: 38 s at n = 37, 66 s at n = 44, 112 s at n = 51, still compiling after 14 minutes at
+// n = 64); above it mk_filter_smooth refuses the variant (MK_ERR_SHAPE)
+constexpr int wave_smoother_max_n = 51;
+
 // backward tape of the wide models (MK_OUT_TAPE; mk_split.hip writes it, mk_dk.hip reads it).  Block of one (model, step):
 // N entries of XS doubles, entry j = [ series part of the vector (N) | side row: factor part (K), s0, s1, s2, 0 ] -- the series
 // part of entry j starts at j * tape_xs_c, its side row at tape_so_c + j * tape_ss_c.  (Round 4 also measured the split

@@ -736,6 +736,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     // KF + 2K replicated ones, and the step's prediction reads the elements back through FS doubles of LDS per model.
     constexpr bool DIST = (KF + K <= H) && (K % 2 == 0) && !MK_TUNE_SKIP(a, 512);
     constexpr int FS = DIST ? H : 0;
+    constexpr int FV = (KF + K + 1) & ~1;        // DIST: the exchange buffer is read back in 16-byte pairs
+    static_assert(!DIST || FV <= FS, "DIST: the pairs read back stay inside the model's exchange buffer");
     __shared__ __attribute__((aligned(16))) double lds[M * (2 * DVS + N * GP + N * KP + 2 * KP + TS * N + N * 2 * KP + FS)];
     double *dbuf = lds + h * 2 * DVS;                                        // d = Pt e_j, two buffers
     double *gtab = lds + M * 2 * DVS + h * N * GP;                           // [N][GP]: loadings of series c, then phi_c
@@ -917,9 +919,9 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
             {
                 double A[K], E[K], W[K], Cl[K], Bq[K], phif[K];
                 if constexpr (DIST) { // the filtered factor block and means of the previous step, every lane a copy for this block only
-                    double fv[KF + K];
+                    double fv[FV]; // the pairs read back: KF + K rounded up to even (odd for K = 2, 6, ...)
 #pragma unroll
-                    for (int e = 0; e < KF + K; e += 2) {
+                    for (int e = 0; e < FV; e += 2) {
                         const v2d t2 = *reinterpret_cast<const v2d *>(fbuf + e);
                         fv[e] = t2.x;
                         fv[e + 1] = t2.y;
@@ -1165,12 +1167,15 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
                 asm volatile("" : "+v"(lv));
                 if (a.tape == 2) { // STATE tape: entry N + k = [ Pt[.][N+k] | PF[.][k] | xf_k | PF[k][k] | NaN | 0 ]
                     if constexpr (DIST) { // the filtered factor block and means: from the exchange buffer
-#pragma unroll
-                        for (int e = 0; e < KF + K; e += 2) {
+                        sfor<0, FV / 2>(MK_LAMBDA(pp) {
+                            constexpr int e = 2 * decltype(pp)::value;
                             const v2d t2 = *reinterpret_cast<const v2d *>(fbuf + e);
-                            if (e < KF) PF[e] = t2.x; else xk[e - KF] = t2.x;
-                            if (e + 1 < KF) PF[e + 1] = t2.y; else xk[e + 1 - KF] = t2.y;
-                        }
+                            if constexpr (e < KF) PF[e] = t2.x;
+                            else xk[e - KF] = t2.x;
+                            if constexpr (e + 1 < KF) PF[e + 1] = t2.y;
+                            else if constexpr (e + 1 < KF + K) xk[e + 1 - KF] = t2.y; // odd KF + K: the pair's tail is padding
+                            static_assert(e < KF + K, "DIST: the factor means read back stay inside xk");
+                        });
                     }
                     sfor<0, K>(MK_LAMBDA(kk) {
                         constexpr int k = decltype(kk)::value;

@@ -1054,7 +1054,7 @@ MK_DECL_WIDE_MFMA(2, 1)
 template <int N, int K>
 static hipError_t launch_wave_nk(const SmootherArgs &a, hipStream_t s)
 {
-    if constexpr (N + K > 16) {
+    if constexpr (N + K > 16 && N + K <= wave_smoother_max_n) {
         if (a.sim_means || a.sim_vars) hipLaunchKernelGGL((smoother_wave_kernel<N, K, true>), dim3((unsigned)a.B), dim3(64), 0, s, a);
         else hipLaunchKernelGGL((smoother_wave_kernel<N, K, false>), dim3((unsigned)a.B), dim3(64), 0, s, a);
         return hipGetLastError();
