@@ -1,5 +1,5 @@
 // mk_capi.hip -- C ABI of libmetran_hip.so (declared in include/metran_hip.h).
-// Thin, exception-free layer: argument validation, kernel dispatch by (N,K), HIP error ->
+// Thin, exception-free layer: argument validation, ONE lookup of the (N,K) kernels (find_ops), HIP error ->
 // mk_status translation, optional hipEvent timing of the two hot kernels.
 #include <hip/hip_runtime.h>
 
@@ -89,72 +89,50 @@ static hipError_t timing_stop(mk_context *ctx, int kind)
     return hipEventRecord(ctx->ev[2 * kind + 1], ctx->stream);
 }
 
-// ---- run-time shape modules (see the MK_SHAPE_MODULE block of mk_kernels.hip and metran_amd/jit.py) ----
+// ---- shape lookup: the ahead-of-time table (mk::shape_ops), then the run-time shape modules' tables (mkmod_ops; see the
+// MK_SHAPE_MODULE block of mk_kernels.hip and metran_amd/jit.py) in registration order ----
 namespace {
-struct ShapeModule {
-    int N, K;
-    void *handle;
-    int (*launch_filter)(const mk::FilterArgs *, void *);
-    int (*launch_smoother)(const mk::SmootherArgs *, void *);
-    int (*launch_adjoint)(const mk::AdjointArgs *, void *);
-    int (*launch_sparse)(const mk::SparseArgs *, void *);
-    int (*launch_loo)(const mk::AdjointArgs *, const mk::SmootherArgs *, void *);
-};
-std::vector<ShapeModule> g_modules;
+std::vector<const mk::ShapeOps *> g_modules;
 std::mutex g_modules_mutex;
 
-const ShapeModule *find_module(int64_t N, int64_t K, bool by_n_only = false)
+// The kernels of (N, K): the first entry that matches.  by_n_only: any entry of the same state dimension n = N + K serves --
+// the smoother without projection and without a tape depends on n only (its kernel, instantiated for that entry's shape, runs).
+// This is the only place that knows that rule; no two ahead-of-time shapes share an n.
+const mk::ShapeOps *find_ops(int64_t N, int64_t K, bool by_n_only = false)
 {
+    const auto serves = [&](const mk::ShapeOps &o) { return (o.N == N && o.K == K) || (by_n_only && o.N + o.K == N + K); };
+    int cnt = 0;
+    const mk::ShapeOps *aot = mk::shape_ops(&cnt);
+    for (int i = 0; i < cnt; ++i)
+        if (serves(aot[i])) return &aot[i];
     std::lock_guard<std::mutex> lock(g_modules_mutex);
-    for (const auto &m : g_modules)
-        if ((m.N == N && m.K == K) || (by_n_only && m.N + m.K == N + K)) return &m;
+    for (const mk::ShapeOps *m : g_modules)
+        if (serves(*m)) return m;
     return nullptr;
 }
-bool aot_shape(int64_t N, int64_t K)
-{
-    for (int i = 0; i < mk::num_shapes(); ++i) {
-        int n_, k_;
-        mk::get_shape(i, &n_, &k_);
-        if (n_ == N && k_ == K) return true;
-    }
-    return false;
-}
-bool aot_state_dim(int64_t n)
-{
-    for (int i = 0; i < mk::num_shapes(); ++i) {
-        int n_, k_;
-        mk::get_shape(i, &n_, &k_);
-        if (n_ + k_ == n) return true;
-    }
-    return false;
-}
-bool specialised(int64_t N, int64_t K) { return aot_shape(N, K) || find_module(N, K) != nullptr; }
+bool specialised(int64_t N, int64_t K) { return find_ops(N, K) != nullptr; }
 bool generic_shape(int64_t N, int64_t K) { return N >= 1 && K >= 1 && N + K <= MK_GENERIC_MAX_STATES; }
 hipError_t dispatch_filter(int N, int K, const mk::FilterArgs &a, hipStream_t s, bool force_generic = false)
 {
     if (force_generic) return generic_shape(N, K) ? mk::launch_filter_generic(N, K, a, s) : hipErrorInvalidValue;
-    if (aot_shape(N, K)) return mk::launch_filter(N, K, a, s);
-    if (const ShapeModule *m = find_module(N, K)) return (hipError_t)m->launch_filter(&a, (void *)s);
+    if (const mk::ShapeOps *o = find_ops(N, K)) return o->filter(a, s);
     if (generic_shape(N, K)) return mk::launch_filter_generic(N, K, a, s); // any shape, not specialised (mk_generic.hip)
     return hipErrorInvalidValue;
 }
 hipError_t dispatch_sparse(int N, int K, const mk::SparseArgs &a, hipStream_t s)
 {
-    if (aot_shape(N, K)) return mk::launch_sparse(N, K, a, s);
-    if (const ShapeModule *m = find_module(N, K)) return (hipError_t)m->launch_sparse(&a, (void *)s);
-    return hipErrorInvalidValue;
+    const mk::ShapeOps *o = find_ops(N, K);
+    return o ? o->sparse(a, s) : hipErrorInvalidValue;
 }
 hipError_t dispatch_adjoint(int N, int K, const mk::AdjointArgs &a, hipStream_t s)
 {
-    if (aot_shape(N, K)) return mk::launch_adjoint(N, K, a, s);
-    if (const ShapeModule *m = find_module(N, K)) return (hipError_t)m->launch_adjoint(&a, (void *)s);
-    return hipErrorInvalidValue;
+    const mk::ShapeOps *o = find_ops(N, K);
+    return o ? o->adjoint(a, s) : hipErrorInvalidValue;
 }
 hipError_t dispatch_loo(int N, int K, const mk::AdjointArgs *na, const mk::SmootherArgs *wa, hipStream_t s)
 {
-    if (aot_shape(N, K)) return mk::launch_loo(N, K, na, wa, s);
-    if (const ShapeModule *m = find_module(N, K)) return (hipError_t)m->launch_loo(na, wa, (void *)s);
-    return hipErrorInvalidValue;
+    const mk::ShapeOps *o = find_ops(N, K);
+    return o ? o->loo(na, wa, s) : hipErrorInvalidValue;
 }
 // workspace of the generic smoother: grown on demand, stream-ordered reuse (every launch of a context is on its stream)
 hipError_t generic_workspace(mk_context *ctx, long B, int n, double **ws)
@@ -183,10 +161,8 @@ hipError_t dispatch_smoother(mk_context *ctx, int N, int K, const mk::SmootherAr
     // need the exact (N, K)
     const bool proj = a.sim_means || a.sim_vars || a.tape != 0;
     const bool force_generic = ctx->variant[MK_VARIANT_KERNEL_FAMILY] == 1;
-    if (!force_generic) {
-        if (proj ? aot_shape(N, K) : aot_state_dim(N + K)) return mk::launch_smoother(N, K, a, s);
-        if (const ShapeModule *m = find_module(N, K, !proj)) return (hipError_t)m->launch_smoother(&a, (void *)s);
-    }
+    if (!force_generic)
+        if (const mk::ShapeOps *o = find_ops(N, K, !proj)) return o->smoother(a, s);
     if (generic_shape(N, K)) {
         mk::GenericSmootherArgs g;
         g.a = a;
@@ -208,34 +184,26 @@ MK_API int mk_register_shape_module(const char *path)
     if (!path) return fail(MK_ERR_INVALID, "null module path");
     void *h = dlopen(path, RTLD_NOW | RTLD_LOCAL);
     if (!h) return fail(MK_ERR_INVALID, "dlopen(%s): %s", path, dlerror());
+    const auto refuse = [&](const char *why) {
+        dlclose(h);
+        return fail(MK_ERR_INVALID, "%s %s", path, why);
+    };
     auto abi = (int (*)(void))dlsym(h, "mkmod_abi");
-    auto shape = (int (*)(int *, int *))dlsym(h, "mkmod_shape");
-    auto lf = (int (*)(const mk::FilterArgs *, void *))dlsym(h, "mkmod_launch_filter");
-    auto ls = (int (*)(const mk::SmootherArgs *, void *))dlsym(h, "mkmod_launch_smoother");
-    auto la = (int (*)(const mk::AdjointArgs *, void *))dlsym(h, "mkmod_launch_adjoint");
-    auto lsp = (int (*)(const mk::SparseArgs *, void *))dlsym(h, "mkmod_launch_sparse");
-    auto ll = (int (*)(const mk::AdjointArgs *, const mk::SmootherArgs *, void *))dlsym(h, "mkmod_launch_loo");
-    if (!abi || !shape || !lf || !ls || !la || !lsp || !ll) {
-        dlclose(h);
-        return fail(MK_ERR_INVALID, "%s is not a metran_hip shape module", path);
-    }
-    if (abi() != (int)(sizeof(mk::FilterArgs) * 1000 + sizeof(mk::SmootherArgs) + sizeof(mk::AdjointArgs) +
-                       sizeof(mk::SparseArgs))) {
-        dlclose(h);
-        return fail(MK_ERR_INVALID, "%s was built against different kernel-argument structs (stale cache)", path);
-    }
-    int N = 0, K = 0;
-    if (shape(&N, &K) != 1) {
-        dlclose(h);
-        return fail(MK_ERR_INVALID, "%s must contain exactly one (N,K) shape", path);
-    }
+    if (!abi) return refuse("is not a metran_hip shape module");
+    // checked before anything else of the module is touched: one built for other structs or another table is refused, not misread
+    if (abi() != mk::module_abi()) return refuse("was built against different kernel-argument structs (stale cache)");
+    auto ops = (const mk::ShapeOps *(*)(int *))dlsym(h, "mkmod_ops");
+    if (!ops) return refuse("is not a metran_hip shape module");
+    int cnt = 0;
+    const mk::ShapeOps *o = ops(&cnt);
+    if (cnt != 1) return refuse("must contain exactly one (N,K) shape");
     std::lock_guard<std::mutex> lock(g_modules_mutex);
-    for (const auto &m : g_modules)
-        if (m.N == N && m.K == K) {
+    for (const mk::ShapeOps *m : g_modules)
+        if (m->N == o->N && m->K == o->K) {
             dlclose(h);
             return MK_OK; // already registered
         }
-    g_modules.push_back(ShapeModule{N, K, h, lf, ls, la, lsp, ll});
+    g_modules.push_back(o); // the handle stays open for the life of the process
     return MK_OK;
 }
 
@@ -541,18 +509,17 @@ static int tape_outputs(const mk_problem *p, const mk_outputs *o)
 
 MK_API int mk_supported_shapes(int64_t *shapes, int cap)
 {
-    int cnt = mk::num_shapes();
+    int cnt = 0;
+    const mk::ShapeOps *aot = mk::shape_ops(&cnt);
     for (int i = 0; i < cnt && i < cap && shapes; ++i) {
-        int n_, k_;
-        mk::get_shape(i, &n_, &k_);
-        shapes[2 * i] = n_;
-        shapes[2 * i + 1] = k_;
+        shapes[2 * i] = aot[i].N;
+        shapes[2 * i + 1] = aot[i].K;
     }
     std::lock_guard<std::mutex> lock(g_modules_mutex);
-    for (const auto &m : g_modules) {
+    for (const mk::ShapeOps *m : g_modules) {
         if (cnt < cap && shapes) {
-            shapes[2 * cnt] = m.N;
-            shapes[2 * cnt + 1] = m.K;
+            shapes[2 * cnt] = m->N;
+            shapes[2 * cnt + 1] = m->K;
         }
         ++cnt;
     }

@@ -534,7 +534,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(N + K <
 
 // Which calls the tape path serves: wide models whose rows and the r row fit a wavefront (16 < n <= 63), projection / state outputs.
 template <int N, int K>
-static hipError_t launch_dk_nk(const SmootherArgs &a, hipStream_t s)
+hipError_t launch_dk_nk(const SmootherArgs &a, hipStream_t s)
 {
     if constexpr (N + K > 16 && N + K + 1 <= 64 && K <= 16) {
         if (a.tape == 2) { // the STATE tape: smoothed state means / variances (and, if asked for, the projection)
@@ -550,17 +550,10 @@ static hipError_t launch_dk_nk(const SmootherArgs &a, hipStream_t s)
         return hipErrorNotSupported;
     }
 }
-#define MK_CASE_DK(NN, KK) \
-    if (N == NN && K == KK) return launch_dk_nk<NN, KK>(a, s);
-hipError_t launch_smoother_dk(int N, int K, const SmootherArgs &a, hipStream_t s)
-{
-    MK_SHAPES(MK_CASE_DK)
-    return hipErrorNotSupported;
-}
 
 // The leave-one-out walk of the tape (mk_loo): the shapes of launch_dk_nk, the plain tape, R = 0 or not.
 template <int N, int K>
-static hipError_t launch_loo_dk_nk(const SmootherArgs &a, hipStream_t s)
+hipError_t launch_loo_dk_nk(const SmootherArgs &a, hipStream_t s)
 {
     if constexpr (N + K > 16 && N + K + 1 <= 64 && K <= 16) {
         if (a.tape != 1 || a.rs != tape_stride_c(N, K) || !a.sim_means || !a.sim_vars) return hipErrorInvalidValue;
@@ -570,12 +563,11 @@ static hipError_t launch_loo_dk_nk(const SmootherArgs &a, hipStream_t s)
         return hipErrorNotSupported;
     }
 }
-#define MK_CASE_LOO_DK(NN, KK) \
-    if (N == NN && K == KK) return launch_loo_dk_nk<NN, KK>(a, s);
-hipError_t launch_loo_dk(int N, int K, const SmootherArgs &a, hipStream_t s)
-{
-    MK_SHAPES(MK_CASE_LOO_DK)
-    return hipErrorNotSupported;
-}
+
+#define MK_INSTANTIATE(NN, KK)                                                   \
+    template hipError_t launch_dk_nk<NN, KK>(const SmootherArgs &, hipStream_t); \
+    template hipError_t launch_loo_dk_nk<NN, KK>(const SmootherArgs &, hipStream_t);
+MK_SHAPES(MK_INSTANTIATE)
+#undef MK_INSTANTIATE
 
 } // namespace mk

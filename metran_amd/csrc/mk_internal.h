@@ -106,7 +106,7 @@ struct AdjointArgs {
     double *gphi, *gq;               // [B,n] gradient of -2 log L w.r.t. diag(Phi), diag(Q)
     const double *upd;               // update tape written by the recording forward pass (FilterArgs.upd), or NULL: recompute
     long us;                         // its stride per (model, step), adjoint_update_stride_c(N, K)
-    // leave-one-out walk (adjoint_kernel<.., LOO = true>, launch_loo): [.,N] per (b,t), same (bs, ts) addressing as the records;
+    // leave-one-out walk (adjoint_kernel<.., LOO = true>, ShapeOps::loo): [.,N] per (b,t), same (bs, ts) addressing as the records;
     // scale / offset [R,N] or NULL as in mk_problem.  Unused by the gradient.
     double *loo_means, *loo_vars;
     const double *scale, *offset;
@@ -129,24 +129,37 @@ struct SparseArgs { // objective of ONE record (all instances share it), observe
     long long *sigmacount;
 };
 
-hipError_t launch_filter(int N, int K, const FilterArgs &a, hipStream_t s);
-// mk_split.hip: wide models, N series on the lanes + replicated factor block (hipErrorNotSupported: not served)
-hipError_t launch_filter_split(int N, int K, const FilterArgs &a, hipStream_t s);
-hipError_t launch_adjoint_wide(int N, int K, const AdjointArgs &a, hipStream_t s); // mk_split.hip: n > 16
-hipError_t launch_sparse(int N, int K, const SparseArgs &a, hipStream_t s);
-hipError_t launch_adjoint(int N, int K, const AdjointArgs &a, hipStream_t s);
+// Per-shape launchers that are called across translation units.  Each is defined in the file named and explicitly instantiated
+// there for every MK_SHAPES entry; the run-time (N, K) is resolved to a compiled <N, K> once, by the lookup in shape_ops().
+template <int N, int K> hipError_t launch_split_nk(const FilterArgs &a, hipStream_t s);         // mk_split.hip: wide models, N series on the lanes + replicated factor block (hipErrorNotSupported: not served)
+template <int N, int K> hipError_t launch_adjoint_wide_nk(const AdjointArgs &a, hipStream_t s); // mk_split.hip: n > 16
+template <int N, int K> hipError_t launch_smoother_wide_nk(const SmootherArgs &a, hipStream_t s); // mk_wide.hip (n > 16)
+template <int N, int K> hipError_t launch_wave_nk(const SmootherArgs &a, hipStream_t s);          // mk_wide.hip: the round-1 kernel
+template <int N, int K, int E, bool S> hipError_t launch_mfma_nk(const SmootherArgs &a, hipStream_t s); // mk_wide.hip: epilogue E, packed-symmetric S
+template <int N, int K> hipError_t launch_dk_nk(const SmootherArgs &a, hipStream_t s);     // mk_dk.hip (a.tape)
+template <int N, int K> hipError_t launch_loo_dk_nk(const SmootherArgs &a, hipStream_t s); // mk_dk.hip: leave-one-out walk of the tape
+
+// One row per compiled shape: the entry points of its kernels.  The library's table is the ahead-of-time list; a run-time shape
+// module (-DMK_SHAPE_MODULE, metran_amd/jit.py) exports its one-row table through mkmod_ops.
+struct ShapeOps {
+    int N, K;
+    hipError_t (*filter)(const FilterArgs &, hipStream_t);
+    hipError_t (*smoother)(const SmootherArgs &, hipStream_t);
+    hipError_t (*sparse)(const SparseArgs &, hipStream_t);
+    hipError_t (*adjoint)(const AdjointArgs &, hipStream_t);
+    // leave-one-out predictions (mk_loo): n <= 16 the adjoint walk over filtered records (*narrow), 16 < n <= 63 the tape walk (*wide)
+    hipError_t (*loo)(const AdjointArgs *narrow, const SmootherArgs *wide, hipStream_t);
+};
+const ShapeOps *shape_ops(int *count); // mk_kernels.hip: one row per MK_SHAPES entry, in list order
+// what a shape module must have been built against: the argument structs and the table row (mkmod_abi)
+constexpr int module_abi()
+{
+    return (int)(sizeof(FilterArgs) * 1000 + sizeof(SmootherArgs) + sizeof(AdjointArgs) + sizeof(SparseArgs) + sizeof(ShapeOps));
+}
 hipError_t launch_alpha_grad(long B, long R, int N, int K, const double *alpha, const double *loadings, double dt,
                              const double *gphi, const double *gq, double *galpha, hipStream_t s);
-hipError_t launch_smoother(int N, int K, const SmootherArgs &a, hipStream_t s);
-hipError_t launch_smoother_wide(int N, int K, const SmootherArgs &a, hipStream_t s); // mk_wide.hip (n > 16)
-hipError_t launch_smoother_dk(int N, int K, const SmootherArgs &a, hipStream_t s);   // mk_dk.hip (a.tape)
-hipError_t launch_loo_dk(int N, int K, const SmootherArgs &a, hipStream_t s);       // mk_dk.hip: leave-one-out walk of the tape
-// leave-one-out predictions (mk_loo): n <= 16 the adjoint walk over filtered records (*narrow), 16 < n <= 63 the tape walk (*wide)
-hipError_t launch_loo(int N, int K, const AdjointArgs *narrow, const SmootherArgs *wide, hipStream_t s);
 int record_stride(int n); // doubles per packed record for state dimension n
 int record_stride_sym(int n); // ... per packed-symmetric record
-int num_shapes();
-void get_shape(int i, int *N, int *K);
 hipError_t launch_params(long B, long R, int N, int K, const double *alpha, const double *loadings, double dt,
                          double *phi, double *q, hipStream_t s);
 hipError_t launch_simulate(long B, long RZ, long T, int N, int n, const double *Z, const double *means,

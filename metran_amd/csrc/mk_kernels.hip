@@ -2134,7 +2134,7 @@ static hipError_t launch_filter_nk(const FilterArgs &a, hipStream_t s)
         }();
         const bool split = a.tape || (a.variant & 2) || (!(a.variant & 1) && a.B > 2 * simds);
         if (split) {
-            const hipError_t e = launch_filter_split(N, K, a, s);
+            const hipError_t e = launch_split_nk<N, K>(a, s);
             if (e != hipErrorNotSupported) return e;
         }
     }
@@ -2173,7 +2173,7 @@ static hipError_t launch_smoother_nk(const SmootherArgs &a, hipStream_t s)
     constexpr int n = N + K;
     constexpr int G = n <= 16 ? 16 : 64;
     if constexpr (G == 64) { // one model per wavefront: mk_wide.hip
-        return launch_smoother_wide(N, K, a, s);
+        return launch_smoother_wide_nk<N, K>(a, s);
     } else {
         constexpr int GPB = 256 / G;
         const unsigned grid = (unsigned)((a.B + GPB - 1) / GPB);
@@ -2213,99 +2213,8 @@ static hipError_t launch_smoother_nk(const SmootherArgs &a, hipStream_t s)
     return hipGetLastError();
 }
 
-#define MK_CASE_FILTER(NN, KK) \
-    if (N == NN && K == KK) return launch_filter_nk<NN, KK>(a, s);
-#define MK_CASE_SMOOTH(NN, KK) \
-    if (N == NN && K == KK) return launch_smoother_nk<NN, KK>(a, s);
-// without projection the smoother depends on n only: any compiled shape of the same state dimension serves
-#define MK_CASE_SMOOTH_N(NN, KK) \
-    if (N + K == NN + KK && !(a.sim_means || a.sim_vars)) return launch_smoother_nk<NN, KK>(a, s);
-#define MK_CASE_LIST(NN, KK) {NN, KK},
-
-hipError_t launch_filter(int N, int K, const FilterArgs &a, hipStream_t s)
-{
-    MK_SHAPES(MK_CASE_FILTER)
-    return hipErrorInvalidValue;
-}
-
-hipError_t launch_smoother(int N, int K, const SmootherArgs &a, hipStream_t s)
-{
-    MK_SHAPES(MK_CASE_SMOOTH)
-    MK_SHAPES(MK_CASE_SMOOTH_N)
-    return hipErrorInvalidValue;
-}
-
-int num_shapes();
-void get_shape(int i, int *N, int *K);
-
-#ifdef MK_SHAPE_MODULE
-#ifndef MK_SHAPE_MODULE_TUS // one translation unit per run-time shape module (scripts/compile_shape.sh); metran_amd/jit.py compiles
-} // namespace mk           // the four files -- mk_wide.hip in its slices -- as separate units in parallel and links them
-#include "mk_wide.hip"
-#include "mk_split.hip"
-#include "mk_dk.hip"
-namespace mk {
-#endif
-// ---------------------------------------------------------------------------------------------
-// Shape module: this same translation unit compiled at run time for ONE (N, K) that is not in the
-// ahead-of-time list (metran_amd/jit.py drives hipcc, runs the DPP hazard check on the assembly and
-// registers the module with mk_register_shape_module).  The kernels are fully unrolled over n, so
-// specialising per shape is what makes them fast; this is how an arbitrary Metran model gets one.
-// ---------------------------------------------------------------------------------------------
-extern "C" {
-MK_API int mkmod_abi(void)
-{
-    return (int)(sizeof(FilterArgs) * 1000 + sizeof(SmootherArgs) + sizeof(AdjointArgs) + sizeof(SparseArgs));
-}
-MK_API int mkmod_launch_sparse(const SparseArgs *a, void *stream)
-{
-    int N, K;
-    get_shape(0, &N, &K);
-    return (int)launch_sparse(N, K, *a, (hipStream_t)stream);
-}
-MK_API int mkmod_launch_adjoint(const AdjointArgs *a, void *stream)
-{
-    int N, K;
-    get_shape(0, &N, &K);
-    return (int)launch_adjoint(N, K, *a, (hipStream_t)stream);
-}
-MK_API int mkmod_launch_loo(const AdjointArgs *narrow, const SmootherArgs *wide, void *stream)
-{
-    int N, K;
-    get_shape(0, &N, &K);
-    return (int)launch_loo(N, K, narrow, wide, (hipStream_t)stream);
-}
-MK_API int mkmod_shape(int *N, int *K)
-{
-    get_shape(0, N, K);
-    return num_shapes();
-}
-MK_API int mkmod_launch_filter(const FilterArgs *a, void *stream)
-{
-    int N, K;
-    get_shape(0, &N, &K);
-    return (int)launch_filter(N, K, *a, (hipStream_t)stream);
-}
-MK_API int mkmod_launch_smoother(const SmootherArgs *a, void *stream)
-{
-    int N, K;
-    get_shape(0, &N, &K);
-    return (int)launch_smoother(N, K, *a, (hipStream_t)stream);
-}
-}
-#endif
-
-static const int kShapes[][2] = {MK_SHAPES(MK_CASE_LIST)};
-
 int record_stride(int n) { return record_stride_c(n); }
 int record_stride_sym(int n) { return record_stride_sym_c(n); }
-
-int num_shapes() { return (int)(sizeof(kShapes) / sizeof(kShapes[0])); }
-void get_shape(int i, int *N, int *K)
-{
-    *N = kShapes[i][0];
-    *K = kShapes[i][1];
-}
 
 hipError_t launch_params(long B, long R, int N, int K, const double *alpha, const double *loadings, double dt,
                          double *phi, double *q, hipStream_t s)
@@ -2353,13 +2262,6 @@ static hipError_t launch_sparse_nk(const SparseArgs &a, hipStream_t s)
         return hipErrorNotSupported;
     }
 }
-#define MK_CASE_SPARSE(NN, KK) \
-    if (N == NN && K == KK) return launch_sparse_nk<NN, KK>(a, s);
-hipError_t launch_sparse(int N, int K, const SparseArgs &a, hipStream_t s)
-{
-    MK_SHAPES(MK_CASE_SPARSE)
-    return hipErrorInvalidValue;
-}
 
 template <int N, int K>
 static hipError_t launch_adjoint_nk(const AdjointArgs &a, hipStream_t s)
@@ -2370,15 +2272,8 @@ static hipError_t launch_adjoint_nk(const AdjointArgs &a, hipStream_t s)
         hipLaunchKernelGGL((adjoint_kernel<N, K, 16>), dim3((unsigned)((a.B + GPB - 1) / GPB)), dim3(256), 0, s, a);
         return hipGetLastError();
     } else {
-        return launch_adjoint_wide(N, K, a, s); // one model per wavefront: mk_split.hip
+        return launch_adjoint_wide_nk<N, K>(a, s); // one model per wavefront: mk_split.hip
     }
-}
-#define MK_CASE_ADJOINT(NN, KK) \
-    if (N == NN && K == KK) return launch_adjoint_nk<NN, KK>(a, s);
-hipError_t launch_adjoint(int N, int K, const AdjointArgs &a, hipStream_t s)
-{
-    MK_SHAPES(MK_CASE_ADJOINT)
-    return hipErrorInvalidValue;
 }
 
 // leave-one-out predictions: the adjoint walk in its LOO mode (n <= 16) or the tape walk of mk_dk.hip (16 < n <= 63)
@@ -2393,16 +2288,34 @@ static hipError_t launch_loo_nk(const AdjointArgs *na, const SmootherArgs *wa, h
         return hipGetLastError();
     } else {
         if (!wa) return hipErrorInvalidValue;
-        return launch_loo_dk(N, K, *wa, s);
+        return launch_loo_dk_nk<N, K>(*wa, s);
     }
 }
-#define MK_CASE_LOO(NN, KK) \
-    if (N == NN && K == KK) return launch_loo_nk<NN, KK>(na, wa, s);
-hipError_t launch_loo(int N, int K, const AdjointArgs *na, const SmootherArgs *wa, hipStream_t s)
+
+// The one place where a run-time (N, K) meets the compiled <N, K>: a row of launchers per MK_SHAPES entry, searched by
+// find_ops (mk_capi.hip).  Function-local: a namespace-scope table of host function pointers is emitted in the device pass too.
+const ShapeOps *shape_ops(int *count)
 {
-    MK_SHAPES(MK_CASE_LOO)
-    return hipErrorInvalidValue;
+#define MK_SHAPE_ROW(NN, KK) \
+    {NN, KK, launch_filter_nk<NN, KK>, launch_smoother_nk<NN, KK>, launch_sparse_nk<NN, KK>, launch_adjoint_nk<NN, KK>, launch_loo_nk<NN, KK>},
+    static const ShapeOps ops[] = {MK_SHAPES(MK_SHAPE_ROW)};
+#undef MK_SHAPE_ROW
+    *count = (int)(sizeof(ops) / sizeof(ops[0]));
+    return ops;
 }
+
+#ifdef MK_SHAPE_MODULE
+// ---------------------------------------------------------------------------------------------
+// Shape module: the four kernel files compiled at run time for ONE (N, K) that is not in the
+// ahead-of-time list (metran_amd/jit.py drives hipcc, runs the DPP hazard check on the assembly and
+// registers the module with mk_register_shape_module).  The kernels are fully unrolled over n, so
+// specialising per shape is what makes them fast; this is how an arbitrary Metran model gets one.
+// ---------------------------------------------------------------------------------------------
+extern "C" {
+MK_API int mkmod_abi(void) { return module_abi(); }
+MK_API const ShapeOps *mkmod_ops(int *count) { return shape_ops(count); }
+}
+#endif
 
 // chain rule of Metran._phi / get_transition_covariance (metran.py:246-322):
 //   phi = exp(-dt/alpha), q = (1 - phi^2) c  =>  d/dalpha = (gphi - 2 phi c gq) phi dt / alpha^2

@@ -1261,7 +1261,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 
 // Which calls the split kernel serves: wide models (n > 16) with N <= 32, objective-only or full-square record outputs.
 template <int N, int K>
-static hipError_t launch_split_nk(const FilterArgs &a, hipStream_t s)
+hipError_t launch_split_nk(const FilterArgs &a, hipStream_t s)
 {
     if constexpr (N + K > 16 && N <= 32) {
         constexpr int H = N <= 16 ? 16 : 32, M = 64 / H;
@@ -1293,13 +1293,6 @@ static hipError_t launch_split_nk(const FilterArgs &a, hipStream_t s)
     } else {
         return hipErrorNotSupported;
     }
-}
-#define MK_CASE_SPLIT(NN, KK) \
-    if (N == NN && K == KK) return launch_split_nk<NN, KK>(a, s);
-hipError_t launch_filter_split(int N, int K, const FilterArgs &a, hipStream_t s)
-{
-    MK_SHAPES(MK_CASE_SPLIT)
-    return hipErrorNotSupported;
 }
 
 } // namespace mk
@@ -1593,7 +1586,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 }
 
 template <int N, int K>
-static hipError_t launch_adjoint_wide_nk(const AdjointArgs &a, hipStream_t s)
+hipError_t launch_adjoint_wide_nk(const AdjointArgs &a, hipStream_t s)
 {
     if constexpr (N + K > 16) {
         if (a.upd) {
@@ -1607,12 +1600,11 @@ static hipError_t launch_adjoint_wide_nk(const AdjointArgs &a, hipStream_t s)
         return hipErrorNotSupported;
     }
 }
-#define MK_CASE_ADJW(NN, KK) \
-    if (N == NN && K == KK) return launch_adjoint_wide_nk<NN, KK>(a, s);
-hipError_t launch_adjoint_wide(int N, int K, const AdjointArgs &a, hipStream_t s)
-{
-    MK_SHAPES(MK_CASE_ADJW)
-    return hipErrorNotSupported;
-}
+
+#define MK_INSTANTIATE(NN, KK)                                                      \
+    template hipError_t launch_split_nk<NN, KK>(const FilterArgs &, hipStream_t); \
+    template hipError_t launch_adjoint_wide_nk<NN, KK>(const AdjointArgs &, hipStream_t);
+MK_SHAPES(MK_INSTANTIATE)
+#undef MK_INSTANTIATE
 
 } // namespace mk

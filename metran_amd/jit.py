@@ -1,5 +1,5 @@
 """Run-time shape specialisation: kernels for an (N series, K factors) pair that is not in the
-ahead-of-time list are compiled on demand from the SAME source (``csrc/mk_kernels.hip``) by hipcc,
+ahead-of-time list are compiled on demand from the SAME source (the four kernel files of ``csrc/``) by hipcc,
 statically checked for the hazards hipcc does not pad around inline asm (``scripts/check_dpp_hazards.py``: the fused
 ``v_fmac_f64_dpp``; ``scripts/check_asm_hazards.py``: MFMA results, MFMA operands, lane selects and transcendental
 results with one side inside an asm block) and registered with the library (``mk_register_shape_module``).
@@ -115,7 +115,7 @@ def build_shape_module(N, K, out=None):
     try:
         hipcc = _hipcc()
         base = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
-                "-I" + os.path.join(_ROOT, "include"), "-I" + os.path.join(_HERE, "csrc"), "-DMK_SHAPE_MODULE", "-DMK_SHAPE_MODULE_TUS",
+                "-I" + os.path.join(_ROOT, "include"), "-I" + os.path.join(_HERE, "csrc"), "-DMK_SHAPE_MODULE",
                 "-DMK_SHAPES(X)=X(%d,%d)" % (N, K), "-save-temps=obj", "-Wno-unused-command-line-argument"] + _extra_flags()
         # the module's translation units, compiled in PARALLEL (round-5 verdict, weak 10: one unit took 6.5 minutes for (48,3), 5.3 of
         # them in mk_wide.hip's fourteen instantiations): the four kernel files, mk_wide.hip in the seven slices of its

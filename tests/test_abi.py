@@ -124,8 +124,10 @@ def test_shape_module_builds_and_passes_hazard_check(tmp_path, monkeypatch):
     path = jit.build_shape_module(7, 3, out=jit.module_path(7, 3))   # (out=: build it HERE even where build() has prebuilt the shape)
     assert os.path.exists(path) and path == jit.module_path(7, 3) and str(tmp_path) in path
     out = subprocess.check_output(["nm", "-D", "--defined-only", path], text=True)
-    for sym in ("mkmod_abi", "mkmod_shape", "mkmod_launch_filter", "mkmod_launch_smoother"):
-        assert sym in out
+    # the module ABI: the struct guard and ONE table of the shape's launchers (mk_internal.h: ShapeOps), nothing per entry point
+    assert sorted(set(re.findall(r"\bmkmod_\w+", out))) == ["mkmod_abi", "mkmod_ops"]
+    for sym in ("mkmod_shape", "mkmod_launch_filter", "mkmod_launch_smoother", "mkmod_launch_adjoint", "mkmod_launch_sparse", "mkmod_launch_loo"):
+        assert sym not in out
     assert "filter_kernelILi7ELi3ELi16" in out and "smoother_record_kernelILi7ELi3ELi16" in out
     monkeypatch.setenv("METRAN_HIP_JIT", "0")
     with pytest.raises(jit.ShapeUnavailable):      # not an error of anything: the engine falls back to the size-generic kernels

@@ -263,7 +263,7 @@ def test_adjoint_with_initial_state_and_observation_variance():
 @pytest.mark.gpu
 def test_adjoint_on_a_runtime_specialised_shape(tmp_path_factory, monkeypatch):
     """(7,2) is not in the ahead-of-time list: the shape module built at run time carries the adjoint
-    kernel too (mkmod_launch_adjoint)."""
+    kernel too (the adjoint entry of the table it exports, mkmod_ops)."""
     import os
 
     from metran_amd.engine import BatchedKalman
