@@ -359,6 +359,44 @@ MK_API int64_t mk_loo_work_stride(int64_t N, int64_t K);
 MK_API int mk_loo(mk_context *ctx, const mk_problem *prob, double *d_work, int time_major, double *d_loo_means,
                   double *d_loo_vars, uint32_t *d_status);
 
+/* Posterior DRAWS of the states and of the projected series: the simulation smoother by mean correction (Durbin & Koopman 2002,
+ * Biometrika 89:603-616).  For the model the filter implements (seqkalmanfilter, metran/kalmanfilter.py:315-333:
+ * x_{-1} ~ N(x0, P0), x_t = phi o x_{t-1} + w_t, y_t = [I | Gamma] x_t + e_t) and path id = s * n_instances + i (draw s of instance i,
+ * record i % n_records), mk_draw_perturb walks time once and writes
+ *     x+_{-1} = L0 z_init,   x+_t = phi o x+_{t-1} + sqrt(q) o z_t[0:n],   y+_t = [I | Gamma] x+_t + sqrt(R) o z_t[n:n+N],
+ *     d_ystar  [ndraws * n_instances, T, N]   y*_{t,j} = y_{t,j} - y+_{t,j} where (t, j) is observed (finite), NaN where it is not,
+ *     d_zxplus [ndraws * n_instances, T, N]   [I | Gamma] x+_t, unscaled                       (may be NULL),
+ *     d_xplus  [ndraws * n_instances, T, n]   x+_t                                             (may be NULL),
+ * all three in the layout of prob->obs_time_major ([T, ndraws * n_instances, .] when set).  d_L0 [n_instances,n,n]: the lower
+ * Cholesky factor of P0, NULL = identity (the default P0); the initial mean of x+ is zero whatever x0 is; the observation normals
+ * are drawn only when prob->d_obsvar is set.  prob->d_x0, d_P0, d_scale, d_offset and warmup are not read.
+ *   The caller then smooths y* with the EXISTING mk_filter_smooth on a derived problem of ndraws * n_instances instances and as
+ * many records (d_obs = d_ystar; d_phi, d_q, d_loadings, d_obsvar, d_scale, d_offset, d_x0, d_P0 replicated per path) and adds the
+ * unconditional part with mk_draw_combine, in place on the smoother's output (both arrays in the layout `time_major`):
+ *     MK_DRAW_SERIES   d_inout [.,T,N] (d_sim_means of y*)  +=  scale[record, j] * d_plus (= d_zxplus)    -- the offset is in sim_means
+ *     MK_DRAW_STATES   d_inout [.,T,n] (smoothed means of y*)  +=  d_plus (= d_xplus)
+ * (prob = the ORIGINAL problem: n_instances, n_records, d_scale).  The smoother is affine in the data, so the result is a draw
+ * from p(x | y) exactly; at an observed cell with R = 0 a series draw returns the observation.
+ *   The normals are counter-based -- a value depends on what it is for, not on the launch that computes it: Philox4x32-10 with
+ * key (seed & 0xffffffff, seed >> 32) and counter (t + 1, c >> 1, first_instance + i, d), t + 1 = 0 the initial state, c the
+ * component (0..n-1 state noise, n..n+N-1 observation noise), d the draw number first_draw + s.  From the output words:
+ * m1 = (w0 >> 6) * 2^26 + (w1 >> 6), u1 = (m1 + 0.5) * 2^-52, likewise m2, u2 from w2, w3; rho = sqrt(-2 ln u1); an even c takes
+ * rho cos(2 pi u2), an odd c rho sin(2 pi u2).  antithetic: draw first_draw + s uses d = (first_draw + s) >> 1 and every normal
+ * times (-1)^((first_draw + s) & 1): the mean of a pair is the smoothed mean exactly.
+ *   mk_draw_normals writes the normals of a block of counters, d_out [ndraws, ninstances, T + 1, ncomp] (time index 0 = the
+ * initial state); raw != 0: the integers m1 (even c) / m2 (odd c) as exact doubles, without the antithetic sign.
+ *   Refusals (no launch): MK_ERR_INVALID for a missing required pointer or a buffer larger than the allocation it points into,
+ * MK_ERR_SHAPE for N + K > mk_generic_max_states(). */
+#define MK_DRAW_SERIES 0
+#define MK_DRAW_STATES 1
+MK_API int mk_draw_perturb(mk_context *ctx, const mk_problem *prob, uint64_t seed, int64_t first_instance, int64_t first_draw,
+                           int64_t ndraws, int antithetic, const double *d_L0, double *d_ystar, double *d_zxplus,
+                           double *d_xplus);
+MK_API int mk_draw_combine(mk_context *ctx, const mk_problem *prob, int64_t ndraws, int what, int time_major,
+                           const double *d_plus, double *d_inout);
+MK_API int mk_draw_normals(mk_context *ctx, uint64_t seed, int64_t first_instance, int64_t ninstances, int64_t first_draw,
+                           int64_t ndraws, int antithetic, int64_t T, int64_t ncomp, int raw, double *d_out);
+
 /* kalmansmoother for B instances (kalmanfilter.py:403-476).  Reads out->d_F and out->d_Pf
  * (as written by mk_filter); predicted moments are recomputed from them (Phi diagonal), so
  * d_Xp/d_Pp are not read.  Writes d_S, d_Ps (either may be NULL), d_status. */

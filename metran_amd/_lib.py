@@ -6,7 +6,7 @@ infrastructure and is never imported from here.)
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint32, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
 
 __all__ = ["MetranHipError", "lib", "library_path", "Problem", "Outputs", "check", "API"]
 
@@ -131,6 +131,10 @@ API = {
                               c_void_p, c_void_p]),
     "mk_loo_work_stride": (c_int64, [c_int64, c_int64]),
     "mk_loo": (c_int, [c_void_p, POINTER(Problem), c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "mk_draw_perturb": (c_int, [c_void_p, POINTER(Problem), c_uint64, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p,
+                                c_void_p]),
+    "mk_draw_combine": (c_int, [c_void_p, POINTER(Problem), c_int64, c_int, c_int, c_void_p, c_void_p]),
+    "mk_draw_normals": (c_int, [c_void_p, c_uint64, c_int64, c_int64, c_int64, c_int64, c_int, c_int64, c_int64, c_int, c_void_p]),
     "mk_standardize": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mk_mask_observations": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "mk_pack_observations": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),

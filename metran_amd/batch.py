@@ -251,6 +251,43 @@ class MetranBatch:
         obs = self.kf.obs
         return torch.where(torch.isfinite(obs), (obs - means) / torch.sqrt(variances), torch.full_like(means, float("nan")))
 
+    # ------------------------------------------------------------------ posterior draws (simulation smoother)
+    def _draws(self, what, ndraws, seed, alpha, antithetic):
+        from .kalmanfilter import check_status
+
+        phi, q = self.kf.params_from_alpha(self._alpha(alpha), dt=self.dt)
+        self.kf.set_scaling(self._std, self._mean)
+        # a model's instance number is its place among ALL models, so its draws do not depend on the number of ranks
+        out = self.kf.draw_smoothed(phi, q, ndraws, seed=seed, what=what, antithetic=antithetic, first_instance=self.shard[0])
+        check_status(out["status"].reshape(-1), "MetranBatch(draws of %s)" % what)
+        return out["draws"]
+
+    def get_simulation_draws(self, ndraws, seed=0, alpha=None, standardized=False, antithetic=False):
+        """``ndraws`` joint realisations of every series given the data, tensor ``[S,R,T,N]``: what ``get_simulated_means`` /
+        ``_variances`` are the pointwise mean and variance of -- but a draw is a whole path, so the uncertainty of a monthly
+        mean, of a yearly minimum or of the time spent below a threshold is read off the ensemble (simulation smoother,
+        Durbin & Koopman 2002; ``BatchedKalman.draw_smoothed``).  Where a series is observed a draw equals the observation.
+        Draw ``s`` of a model is fixed by ``seed``: asking for more draws extends the ensemble, it does not change it."""
+        draws = self._draws("series", ndraws, seed, alpha, antithetic)  # original units
+        if standardized:
+            draws = (draws - self._mean[None, :, None, :]) / self._std[None, :, None, :]
+        return draws
+
+    def get_state_draws(self, ndraws, seed=0, alpha=None, antithetic=False):
+        """``ndraws`` joint realisations of the states given the data, tensor ``[S,R,T,N+K]`` (``get_state_means`` is their
+        pointwise mean)."""
+        return self._draws("states", ndraws, seed, alpha, antithetic)
+
+    def get_simulation_draw(self, r, name, ndraws, seed=0, alpha=None, standardized=False, antithetic=False):
+        """Draws of series ``name`` of model ``r``: DataFrame on the model's index, one column ``draw<s>`` per draw."""
+        from pandas import DataFrame
+
+        j = self._series(r, name)
+        draws = self.get_simulation_draws(ndraws, seed, alpha, standardized, antithetic)
+        L = int(self.batch.lengths[r])
+        return DataFrame(draws[:, r, :L, j].transpose(0, 1).cpu().numpy(), index=self.batch.index[r],
+                         columns=["draw%d" % s for s in range(int(ndraws))])
+
     def _series(self, r, name):
         names = list(self.batch.names[r])
         if name not in names:

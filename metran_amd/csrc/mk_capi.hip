@@ -11,6 +11,7 @@
 #include <vector>
 #include <new>
 
+#include "draw_kernels.h"
 #include "mk_generic.h"
 #include "mk_internal.h"
 #include "mk_lbfgs.h"
@@ -1122,6 +1123,137 @@ MK_API int mk_loo(mk_context *ctx, const mk_problem *p, double *d_work, int time
     MK_HIP(timing_start(ctx, 1));
     MK_HIP(dispatch_loo((int)p->N, (int)p->K, nullptr, &a, ctx->stream));
     MK_HIP(timing_stop(ctx, 1));
+    return MK_OK;
+}
+
+// ---- simulation smoother (Durbin & Koopman 2002): the unconditional paths and the perturbed records (draw_kernels.hip) ----
+// Each buffer must end inside the device allocation it starts in (as in mk_loo: an interior pointer of a pooled allocation passes
+// whenever the pool's block is large enough -- the check catches a buffer that is too small, not every misuse).
+struct draw_buffer { const void *ptr; int64_t doubles; const char *name; };
+static int draw_buffers_fit(const char *who, const draw_buffer *bufs, int count)
+{
+    for (int k = 0; k < count; ++k) {
+        const draw_buffer &b = bufs[k];
+        if (!b.ptr) continue;
+        hipDeviceptr_t base = nullptr;
+        size_t bytes = 0;
+        if (hipMemGetAddressRange(&base, &bytes, (hipDeviceptr_t)b.ptr) != hipSuccess) {
+            (void)hipGetLastError(); // not a hipMalloc allocation: its size cannot be known here
+            continue;
+        }
+        if ((const char *)b.ptr + b.doubles * (int64_t)sizeof(double) > (const char *)base + bytes)
+            return fail(MK_ERR_INVALID, "%s: %s is larger than the device allocation it points into", who, b.name);
+    }
+    return MK_OK;
+}
+
+static int draw_counts(const char *who, int64_t first_instance, int64_t first_draw, int64_t ndraws)
+{
+    if (ndraws < 1 || first_draw < 0 || first_instance < 0)
+        return fail(MK_ERR_INVALID, "%s: need ndraws >= 1, first_draw >= 0 and first_instance >= 0 (got %lld, %lld, %lld)", who,
+                    (long long)ndraws, (long long)first_draw, (long long)first_instance);
+    return MK_OK;
+}
+
+MK_API int mk_draw_perturb(mk_context *ctx, const mk_problem *p, uint64_t seed, int64_t first_instance, int64_t first_draw,
+                           int64_t ndraws, int antithetic, const double *d_L0, double *d_ystar, double *d_zxplus, double *d_xplus)
+{
+    MK_CTX(ctx);
+    if (!p) return fail(MK_ERR_INVALID, "null mk_problem");
+    if (p->N >= 1 && p->K >= 1 && p->N + p->K > MK_GENERIC_MAX_STATES)
+        return fail(MK_ERR_SHAPE, "mk_draw_perturb: N=%lld, K=%lld has %lld states; the library serves N + K <= %d", (long long)p->N,
+                    (long long)p->K, (long long)(p->N + p->K), MK_GENERIC_MAX_STATES);
+    if (int rc = check_problem(p)) return rc;
+    if (int rc = draw_counts("mk_draw_perturb", first_instance, first_draw, ndraws)) return rc;
+    if (!p->d_obs || !p->d_loadings) return fail(MK_ERR_INVALID, "mk_draw_perturb: d_obs and d_loadings are required");
+    if (!d_ystar) return fail(MK_ERR_INVALID, "mk_draw_perturb: d_ystar is required");
+    const int64_t n = p->N + p->K, SB = ndraws * p->n_instances;
+    const draw_buffer bufs[4] = {{d_ystar, SB * p->T * p->N, "d_ystar (ndraws * n_instances * T * N doubles)"},
+                                 {d_zxplus, SB * p->T * p->N, "d_zxplus (ndraws * n_instances * T * N doubles)"},
+                                 {d_xplus, SB * p->T * n, "d_xplus (ndraws * n_instances * T * (N + K) doubles)"},
+                                 {d_L0, p->n_instances * n * n, "d_L0 (n_instances * (N + K)^2 doubles)"}};
+    if (int rc = draw_buffers_fit("mk_draw_perturb", bufs, 4)) return rc;
+    mk::DrawArgs a;
+    memset(&a, 0, sizeof(a));
+    a.B = p->n_instances;
+    a.R = p->n_records;
+    a.T = p->T;
+    a.N = (int)p->N;
+    a.K = (int)p->K;
+    a.S = ndraws;
+    a.bs = p->obs_time_major ? 1 : p->T;
+    a.ts = p->obs_time_major ? SB : 1;
+    a.obs_bs = p->obs_time_major ? 1 : p->T;
+    a.obs_ts = p->obs_time_major ? p->n_records : 1;
+    a.seed = seed;
+    a.first_instance = first_instance;
+    a.first_draw = first_draw;
+    a.antithetic = antithetic != 0;
+    a.obs = p->d_obs;
+    a.phi = p->d_phi;
+    a.q = p->d_q;
+    a.loadings = p->d_loadings;
+    a.obsvar = p->d_obsvar;
+    a.L0 = d_L0;
+    a.ystar = d_ystar;
+    a.zxplus = d_zxplus;
+    a.xplus = d_xplus;
+    MK_HIP(mk::launch_draw_perturb(a, ctx->stream));
+    return MK_OK;
+}
+
+MK_API int mk_draw_combine(mk_context *ctx, const mk_problem *p, int64_t ndraws, int what, int time_major, const double *d_plus,
+                           double *d_inout)
+{
+    MK_CTX(ctx);
+    if (!p) return fail(MK_ERR_INVALID, "null mk_problem");
+    if (p->n_instances <= 0 || p->n_records <= 0 || p->n_records > p->n_instances || p->T <= 0 || p->N <= 0 || p->K <= 0 || ndraws < 1)
+        return fail(MK_ERR_INVALID, "mk_draw_combine: need 1 <= n_records <= n_instances, T, N, K >= 1 and ndraws >= 1");
+    if (what != MK_DRAW_SERIES && what != MK_DRAW_STATES)
+        return fail(MK_ERR_INVALID, "mk_draw_combine: what must be MK_DRAW_SERIES or MK_DRAW_STATES (got %d)", what);
+    if (!d_plus || !d_inout) return fail(MK_ERR_INVALID, "mk_draw_combine: d_plus and d_inout are required");
+    const int64_t W = what == MK_DRAW_SERIES ? p->N : p->N + p->K, SB = ndraws * p->n_instances;
+    const draw_buffer bufs[2] = {{d_plus, SB * p->T * W, "d_plus (ndraws * n_instances * T * width doubles)"},
+                                 {d_inout, SB * p->T * W, "d_inout (ndraws * n_instances * T * width doubles)"}};
+    if (int rc = draw_buffers_fit("mk_draw_combine", bufs, 2)) return rc;
+    mk::DrawCombineArgs a;
+    memset(&a, 0, sizeof(a));
+    a.SB = SB;
+    a.B = p->n_instances;
+    a.R = p->n_records;
+    a.T = p->T;
+    a.W = (int)W;
+    a.time_major = time_major != 0;
+    a.scale = what == MK_DRAW_SERIES ? p->d_scale : nullptr;
+    a.plus = d_plus;
+    a.inout = d_inout;
+    MK_HIP(mk::launch_draw_combine(a, ctx->stream));
+    return MK_OK;
+}
+
+MK_API int mk_draw_normals(mk_context *ctx, uint64_t seed, int64_t first_instance, int64_t ninstances, int64_t first_draw, int64_t ndraws,
+                           int antithetic, int64_t T, int64_t ncomp, int raw, double *d_out)
+{
+    MK_CTX(ctx);
+    if (int rc = draw_counts("mk_draw_normals", first_instance, first_draw, ndraws)) return rc;
+    if (ninstances < 1 || T < 0 || ncomp < 1 || ncomp > 2 * MK_GENERIC_MAX_STATES)
+        return fail(MK_ERR_INVALID, "mk_draw_normals: need ninstances >= 1, T >= 0 and 1 <= ncomp <= %d", 2 * MK_GENERIC_MAX_STATES);
+    if (!d_out) return fail(MK_ERR_INVALID, "mk_draw_normals: d_out is required");
+    const draw_buffer buf = {d_out, ndraws * ninstances * (T + 1) * ncomp, "d_out (ndraws * ninstances * (T + 1) * ncomp doubles)"};
+    if (int rc = draw_buffers_fit("mk_draw_normals", &buf, 1)) return rc;
+    mk::DrawNormalsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.seed = seed;
+    a.first_instance = first_instance;
+    a.ninstances = ninstances;
+    a.first_draw = first_draw;
+    a.ndraws = ndraws;
+    a.T = T;
+    a.ncomp = (int)ncomp;
+    a.antithetic = antithetic != 0;
+    a.raw = raw != 0;
+    a.out = d_out;
+    MK_HIP(mk::launch_draw_normals(a, ctx->stream));
     return MK_OK;
 }
 

@@ -746,6 +746,160 @@ class BatchedKalman:
                              self._p(res["loo_means"]), self._p(res["loo_vars"]), self._p(res["status"])))
         return res
 
+    # ------------------------------------------------------------------ posterior draws (simulation smoother)
+    def _draw_perturb(self, prob, B, ndraws, seed, first_instance, first_draw, antithetic, L0, want_zx, want_x):
+        """``mk_draw_perturb`` for ``ndraws`` draws of the B instances of ``prob``: ``(ystar, zxplus or None, xplus or None)``,
+        logical ``[ndraws*B,T,.]`` in the engine's layout."""
+        SB = ndraws * B
+        ystar = self._empty_bt(SB, self.T, self.N)
+        zx = self._empty_bt(SB, self.T, self.N) if want_zx else None
+        xp = self._empty_bt(SB, self.T, self.n) if want_x else None
+        self._bind_stream()
+        check(self._L.mk_draw_perturb(self._ctx, ctypes.byref(prob), int(seed) & (2 ** 64 - 1), int(first_instance), int(first_draw),
+                                      int(ndraws), 1 if antithetic else 0, self._p(L0), self._p(ystar), self._p(zx), self._p(xp)))
+        return ystar, zx, xp
+
+    def _adopt_records(self, obs, loadings, obsvar=None, scale=None, offset=None):
+        """Take device-resident records and their per-record arrays as they are -- ``obs [R,T,N]`` already in this engine's
+        layout with NaN for missing, ``loadings [R,N,K]``, ``obsvar / scale / offset [R,N]`` or None -- with everything
+        ``set_observations`` + ``set_loadings`` + ``set_scaling`` guarantee except the copies: shapes checked, kernels for
+        (N, K) ensured, anything that belonged to the previous records (unmasked copy, pending forward pass, the context's
+        cached observed-step list) dropped."""
+        torch = _torch()
+        for name, t in (("obs", obs), ("loadings", loadings), ("obsvar", obsvar), ("scale", scale), ("offset", offset)):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.device == self.device):
+                raise ValueError("%s must be a float64 tensor on %s" % (name, self.device))
+        if obs.ndim != 3 or self._layout(obs) is not obs:
+            raise ValueError("obs must be [R,T,N] in the engine's layout")
+        R, T, N = (int(v) for v in obs.shape)
+        if loadings.ndim != 3 or tuple(loadings.shape[:2]) != (R, N) or not loadings.is_contiguous():
+            raise ValueError("loadings must be a contiguous [R=%d,N=%d,K] tensor, got %s" % (R, N, tuple(loadings.shape)))
+        for name, t in (("obsvar", obsvar), ("scale", scale), ("offset", offset)):
+            if t is not None and (tuple(t.shape) != (R, N) or not t.is_contiguous()):
+                raise ValueError("%s must be a contiguous [%d,%d] tensor" % (name, R, N))
+        shape_before = (self.N, getattr(self, "K", None))
+        self.obs, self.R, self.T, self.N = obs, R, T, N
+        self.loadings, self.K = loadings, int(loadings.shape[2])
+        self.obsvar, self.scale, self.offset = obsvar, scale, offset
+        self._obs_unmasked = None
+        self._grad_pending = self._grad_alpha = None
+        if (self.N, self.K) != shape_before:
+            self._ensure_kernels()
+        check(self._L.mk_observations_changed(self._ctx))
+        return self
+
+    def _draw_sub_engine(self, B):
+        """The engine that smooths the perturbed records: same device, layout, kernels and projection path as this one (the
+        wide filter's batch-size rule "auto" pinned to what it picks for this engine's B instances, so that a draw does not
+        depend on how many draws share its launch)."""
+        sub = getattr(self, "_draw_kf", None)
+        if sub is None or sub._ctx is None:
+            sub = self._draw_kf = BatchedKalman(self.device.index, layout="time_major" if self.time_major else "model_major",
+                                                packed_sym=False)
+        sub.projection_path = self.projection_path
+        for which in self._VARIANTS:
+            sub.set_variant(which, self.get_variant(which))
+        if self.get_variant("wide_filter") == "auto":
+            sub.set_variant("wide_filter", self.resolved_wide_filter(B))
+        return sub
+
+    def _draw_bytes_per_draw(self, B, what):
+        """Device bytes one draw of B instances needs next to the result: y*, the unconditional part, and the smoothing pass's
+        record array / tape and moments."""
+        N, n = self.N, self.n
+        if what == "series":
+            stride = int(self._L.mk_tape_stride(N, self.K)) if self.tape_path() else self.record_stride()
+            per_step = 2 * N + stride + 2 * N
+        else:
+            stride = int(self._L.mk_state_tape_stride(N, self.K)) if self.state_tape_path() else self.record_stride()
+            per_step = N + n + stride + 2 * n
+        return 8.0 * B * self.T * per_step
+
+    def draw_smoothed(self, phi, q, ndraws, seed=0, what="series", x0=None, P0=None, antithetic=False, first_draw=0,
+                      first_instance=0, chunk=None):
+        """Joint posterior DRAWS given the data -- the simulation smoother by mean correction (Durbin & Koopman 2002): for every
+        draw one unconditional simulation of the model (``mk_draw_perturb``: counter-based normals, so draw ``s`` of instance
+        ``i`` is the same numbers whatever launch computes it), one smoothing pass of the perturbed record through the route
+        ``simulate_smoothed`` (``what="series"``) or ``smooth_state_variances`` (``"states"``) takes for this engine, and the
+        sum of the two (``mk_draw_combine``).  Series draws are in the units of ``set_scaling``; at an observed cell without
+        observation variance a series draw is the observation.  ``antithetic``: draws 2k and 2k + 1 mirror each other around
+        the smoothed mean.  Draws run in chunks sized by the free device memory (``chunk=`` forces a size); the result does not
+        depend on the chunk size.  ``first_draw`` / ``first_instance`` number this call's draws / instances within a larger
+        ensemble.  Returns ``{"draws": [S,B,T,N] or [S,B,T,n], "status": [S,B]}``."""
+        torch = _torch()
+        if what not in ("series", "states"):
+            raise ValueError("what must be 'series' or 'states'")
+        S = int(ndraws)
+        if S < 1:
+            raise ValueError("ndraws must be >= 1")
+        if self.packed_sym:
+            raise MetranHipError("draw_smoothed needs a full-square engine (packed_sym=False)")
+        prob, keep, B = self._problem(phi, q, 1, x0, P0)
+        phi_, q_, x0_, P0_ = keep
+        L0 = torch.linalg.cholesky(P0_).contiguous() if P0_ is not None else None
+        series = what == "series"
+        W = self.N if series else self.n
+        draws = torch.empty((S, B, self.T, W), dtype=torch.float64, device=self.device)
+        status = torch.empty((S, B), dtype=torch.int32, device=self.device)
+        ws = getattr(self, "_draw_ws", None)
+        if chunk is None:
+            per = self._draw_bytes_per_draw(B, what)
+            have = ws["bytes"] if ws is not None and ws["key"][:2] == (what, B) and ws["key"][3:6] == (self.T, self.N, self.K) else 0.0
+            room = max(have, 0.8 * float(torch.cuda.mem_get_info(self.device)[0]))
+            chunk = int(min(S, room // per))
+            if chunk < 1:
+                raise MemoryError("one draw of %d instances needs %.1f GB (T=%d, N=%d, K=%d); %.1f GB are free -- draw fewer "
+                                  "instances at a time" % (B, per / 1e9, self.T, self.N, self.K, room / 0.8 / 1e9))
+        chunk = max(1, min(int(chunk), S))
+        sub = self._draw_sub_engine(B)
+        rec = torch.arange(B, device=self.device) % self.R
+        rep = lambda a, c, *ones: None if a is None else a.repeat(c, *ones)  # noqa: E731
+        res = out = None
+        for s0 in range(0, S, chunk):
+            c = min(chunk, S - s0)
+            ystar, zx, xp = self._draw_perturb(prob, B, c, seed, first_instance, first_draw + s0, antithetic, L0, series, not series)
+            # the derived problem: one record per path, this engine's CURRENT loadings / variances / scaling replicated over the draws
+            sub._adopt_records(ystar, rep(self.loadings[rec], c, 1, 1), rep(None if self.obsvar is None else self.obsvar[rec], c, 1),
+                               rep(None if self.scale is None else self.scale[rec], c, 1),
+                               rep(None if self.offset is None else self.offset[rec], c, 1))
+            # the workspace is kept between chunks (and calls) of one size AND one smoothing route
+            route = (sub.tape_path() if series else sub.state_tape_path(), sub.get_variant("kernel_family"))
+            key = (what, B, c, self.T, self.N, self.K) + route
+            if ws is None or ws["key"] != key:
+                res = out = ws = self._draw_ws = None   # the old workspace goes before the new one comes (a tail chunk, another route)
+                buffers = sub.alloc_projection(c * B) if series else sub.alloc_state_variances(c * B)
+                ws = self._draw_ws = {"key": key, "buffers": buffers, "bytes": c * self._draw_bytes_per_draw(B, what)}
+                del buffers
+            ws["buffers"]["status"].zero_()
+            kw = dict(x0=rep(x0_, c, 1), P0=rep(P0_, c, 1, 1), buffers=ws["buffers"])
+            res = (sub.simulate_smoothed if series else sub.smooth_state_variances)(rep(phi_, c, 1), rep(q_, c, 1), **kw)
+            out = res["sim_means"] if series else res["S"]
+            self._bind_stream()
+            check(self._L.mk_draw_combine(self._ctx, ctypes.byref(prob), c, 0 if series else 1, 1 if self.time_major else 0,
+                                          self._p(zx if series else xp), self._p(out)))
+            draws[s0:s0 + c] = out.unflatten(0, (c, B))
+            status[s0:s0 + c] = res["status"].view(c, B)
+            sub.obs = None   # y* of this chunk is done with
+        return {"draws": draws, "status": status}
+
+    def simulate_unconditional(self, phi, q, ndraws, seed=0, P0=None, antithetic=False, first_draw=0, first_instance=0):
+        """Unconditional simulations of the model (the first half of ``draw_smoothed``, same kernel, same normals): ``xplus
+        [S,B,T,n]`` state paths started from N(0, P0), ``zxplus [S,B,T,N]`` their projections ``[I | loadings] x+`` (unscaled)
+        and ``yplus [S,B,T,N]`` the simulated records (with observation noise where observation variances are set)."""
+        torch = _torch()
+        S = int(ndraws)
+        if S < 1:
+            raise ValueError("ndraws must be >= 1")
+        held = self.obs
+        try:   # against an all-zero record the perturbed record is -y+ at every cell
+            self.obs = self._layout(torch.zeros((self.R, self.T, self.N), dtype=torch.float64, device=self.device))
+            prob, keep, B = self._problem(phi, q, 1, None, P0)
+            L0 = torch.linalg.cholesky(keep[3]).contiguous() if keep[3] is not None else None
+            ystar, zx, xp = self._draw_perturb(prob, B, S, seed, first_instance, first_draw, antithetic, L0, True, True)
+        finally:
+            self.obs = held
+        return {"xplus": xp.unflatten(0, (S, B)), "zxplus": zx.unflatten(0, (S, B)), "yplus": (-ystar).unflatten(0, (S, B))}
+
     def state_tape_path(self):
         """True when ``smooth_state_variances`` runs over the STATE tape (``MK_OUT_TAPE | MK_OUT_VAR_ONLY``: the tape of
         ``tape_path`` plus K factor entries per step; ``mk_dk.hip`` STATE = true): the shapes of ``tape_path`` with zero
