@@ -241,7 +241,8 @@ MK_API int mk_memset(mk_context *ctx, void *d_dst, int value, size_t bytes);
 
 /* ---- the hot path --------------------------------------------------------------------------- */
 /* Metran._get_matrices restricted to the diagonals (metran/metran.py:246-322):
- *   phi = exp(-dt/alpha);  q_i = (1-phi_i^2)(1 - sum_k loadings[i,k]^2) for i<N, 1-phi_i^2 else. */
+ *   phi = exp(-dt/alpha);  q_i = (1-phi_i^2)(1 - sum_k loadings[i,k]^2) for i<N, 1-phi_i^2 else.
+ * Instance b uses d_loadings[b % R].  K = 0 (no common factor) is served, and d_loadings may then be NULL. */
 MK_API int mk_params_from_alpha(mk_context *ctx, int64_t B, int64_t R, int64_t N, int64_t K,
                                 const double *d_alpha /* [B,n] */,
                                 const double *d_loadings /* [R,N,K] */, double dt,
@@ -339,7 +340,8 @@ MK_API int mk_loglik_grad_phases(mk_context *ctx, const mk_problem *prob, double
 MK_API int64_t mk_adjoint_update_stride(int64_t N, int64_t K);
 MK_API int mk_set_adjoint_updates(mk_context *ctx, double *d_buf, int64_t capacity_doubles);
 /* Chain rule of mk_params_from_alpha: d/dalpha = (gphi - 2 phi c gq) phi dt / alpha^2, c = 1 - sum_k
- * loadings^2 for the series, 1 for the factors (metran/metran.py:246-322). */
+ * loadings^2 for the series, 1 for the factors (metran/metran.py:246-322).  As mk_params_from_alpha: instance b uses
+ * d_loadings[b % R], and d_loadings may be NULL when K = 0. */
 MK_API int mk_alpha_grad(mk_context *ctx, int64_t B, int64_t R, int64_t N, int64_t K,
                          const double *d_alpha /* [B,n] */, const double *d_loadings /* [R,N,K] */,
                          double dt, const double *d_gphi, const double *d_gq, double *d_galpha /* [B,n] */);
@@ -452,7 +454,8 @@ MK_API int mk_allreduce_sum(mk_context *ctx, double *d_buf, int64_t count);
 /* Metran.standardize (metran/metran.py:102-121) for R models: per series, subtract the mean and
  * divide by the standard deviation (pandas semantics: NaN skipped, ddof = 1).  d_in / d_out are
  * [R,T,N] (or [T,R,N] when time_major != 0); d_out may equal d_in or be NULL (statistics only);
- * d_mean / d_std [R,N] may be NULL.  N <= 64. */
+ * d_mean / d_std [R,N] may be NULL.  N <= 64.  +-inf is a value: a series holding one has mean +-inf (NaN with both signs)
+ * and std NaN, so all of it standardises to NaN -- as do a series never observed, observed once (std NaN) or constant (std 0). */
 MK_API int mk_standardize(mk_context *ctx, int64_t R, int64_t T, int64_t N, int time_major,
                           const double *d_in, double *d_out, double *d_mean, double *d_std);
 
@@ -472,7 +475,10 @@ MK_API int mk_pack_observations(mk_context *ctx, int64_t R, int64_t T, int64_t N
 
 /* ---- batched factor analysis (what produces the loadings; metran/factoranalysis.py) ----------- */
 /* FactorAnalysis._get_correlations (factoranalysis.py:404-418; pandas DataFrame.corr, pearson, pairwise
- * complete): d_corr [R,N,N] from NaN-encoded d_obs [R,T,N] ([T,R,N] when time_major != 0).  N <= 64. */
+ * complete): d_corr [R,N,N] from NaN-encoded d_obs [R,T,N] ([T,R,N] when time_major != 0).  N <= 64.  An entry is NaN when
+ * the pair has no common row or one of the two series is constant on the common rows (the diagonal is 1 or NaN by the same
+ * rule).  +-inf is a value, not a missing one: every pair that has an inf among its common rows is NaN (two-pass definition;
+ * pandas' online algorithm returns an artefact there), and the other pairs are not affected. */
 MK_API int mk_fa_correlation(mk_context *ctx, int64_t R, int64_t T, int64_t N, int time_major,
                              const double *d_obs, double *d_corr);
 /* _get_eigval (:420-460), _maptest (:220-312), the factor-count rules of solve (:66-82; maxfactors <= 0 =

@@ -1402,7 +1402,7 @@ MK_API int mk_alpha_grad(mk_context *ctx, int64_t B, int64_t R, int64_t N, int64
                          const double *loadings, double dt, const double *gphi, const double *gq, double *galpha)
 {
     MK_CTX(ctx);
-    if (B <= 0 || R <= 0 || N <= 0 || K < 0 || !alpha || !loadings || !gphi || !gq || !galpha)
+    if (B <= 0 || R <= 0 || N <= 0 || K < 0 || !alpha || (K > 0 && !loadings) || !gphi || !gq || !galpha)
         return fail(MK_ERR_INVALID, "mk_alpha_grad: bad argument");
     MK_HIP(mk::launch_alpha_grad(B, R, (int)N, (int)K, alpha, loadings, dt, gphi, gq, galpha, ctx->stream));
     return MK_OK;

@@ -144,6 +144,9 @@ __device__ __forceinline__ int rank_desc(const double *A, int n, int k)
 // (NaN = missing; the daily-grid padding of Metran.oseries, metran.py:571), two passes (means, then centred
 // sums).  One block per record, one thread per pair (i <= j).  corr [R,N,N] symmetric, diagonal 1 (NaN when a
 // series has fewer than two common observations or zero variance -- pandas gives NaN there as well).
+// +-inf is a value, not a missing one: its deviation from the (infinite) mean is NaN, so every pair with an inf among its
+// common rows comes out NaN and no other pair is affected.  pandas' online algorithm returns an artefact there (-1.0 against
+// an unrelated series has been seen), so that case is checked against the two-pass definition, not against pandas.
 // ---------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) fa_corr_kernel(long R, long T, int N, long bs, long ts, const double *obs, double *corr)
 {
