@@ -5,7 +5,10 @@ out in mk_kernels.hip::adjoint_kernel.  Checked against central differences in t
 import numpy as np
 
 
-def forward(y, phi, q, G, warmup=1, x0=None, P0=None, R=None):
+def forward(y, phi, q, G, warmup=1, x0=None, P0=None, R=None, weight_index="compressed"):
+    """``weight_index``: "compressed" -- the warm-up counts OBSERVED steps, as get_mle does; "time" -- the deliberately wrong
+    form that counts time steps (tests/test_call_forms.py forms wrong references with it; nothing else may)."""
+    assert weight_index in ("compressed", "time")
     T, N = y.shape
     n = N + G.shape[1]
     x = np.zeros(n) if x0 is None else np.array(x0, float)
@@ -30,7 +33,7 @@ def forward(y, phi, q, G, warmup=1, x0=None, P0=None, R=None):
             sig += v * v / f
             det += np.log(f)
         if obs:
-            if sc >= warmup:
+            if (sc if weight_index == "compressed" else t) >= warmup:
                 mle += sig + det
             sc += 1
         if t >= warmup:
@@ -39,9 +42,9 @@ def forward(y, phi, q, G, warmup=1, x0=None, P0=None, R=None):
     return mle + nobs * np.log(2 * np.pi), F, Pf, sc
 
 
-def gradient(y, phi, q, G, warmup=1, x0=None, P0=None, R=None):
+def gradient(y, phi, q, G, warmup=1, x0=None, P0=None, R=None, weight_index="compressed"):
     """-> (mle, d mle/d phi, d mle/d q)"""
-    mle, F, Pf, sctot = forward(y, phi, q, G, warmup, x0, P0, R)
+    mle, F, Pf, sctot = forward(y, phi, q, G, warmup, x0, P0, R, weight_index)
     R = np.zeros(y.shape[1]) if R is None else R
     T, N = y.shape
     n = N + G.shape[1]
@@ -55,7 +58,7 @@ def gradient(y, phi, q, G, warmup=1, x0=None, P0=None, R=None):
         P = np.outer(phi, phi) * Pprev + np.diag(q)
         obs = [j for j in range(N) if np.isfinite(y[t, j])]
         if obs:
-            w = 1.0 if sctot - rem - 1 >= warmup else 0.0
+            w = 1.0 if (sctot - rem - 1 if weight_index == "compressed" else t) >= warmup else 0.0
             rem += 1
             st = []
             for j in obs:
