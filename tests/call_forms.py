@@ -104,18 +104,20 @@ def variant(g, **kw):
     return out
 
 
-def shared_group(N, K, T, R, S, seed):
+def shared_group(N, K, T, R, S, seed, patterns=MISSINGNESS, usable=_usable):
     """R records and B = S * R instances in the library's order (instance s * R + r reads record r).  dict: obs [R,T,N],
-    loadings [R,N,K], obsvar / scale / offset [R,N], patterns [R]; phi / q / x0 [B,n], P0 [B,n,n]; N, K, T, R, S, B."""
+    loadings [R,N,K], obsvar / scale / offset [R,N], patterns [R]; phi / q / x0 [B,n], P0 [B,n,n]; N, K, T, R, S, B.
+    ``patterns`` / ``usable``: the missingness patterns taken in turn and the condition a drawn record is redrawn until it
+    meets (tests/time_axis.py has its own: it edits the records afterwards)."""
     rng = np.random.default_rng([int(seed), N, K, T, R, S])
     n, B = N + K, S * R
     g = dict(N=N, K=K, T=T, R=R, S=S, B=B, obs=np.empty((R, T, N)), loadings=np.empty((R, N, K)), patterns=[])
     rphi, rq = np.empty((R, n)), np.empty((R, n))
     for r in range(R):
-        pat = MISSINGNESS[r % len(MISSINGNESS)]
+        pat = patterns[r % len(patterns)]
         while True:
             y, phi, q, load = hard_models.draw_model(rng, N, K, T, pat)
-            if phi.max() < 1.0 - 1e-3 and _usable(pat, y, [int(np.isfinite(o).any(1).sum()) for o in g["obs"][:r]]):
+            if phi.max() < 1.0 - 1e-3 and usable(pat, y, [int(np.isfinite(o).any(1).sum()) for o in g["obs"][:r]]):
                 break
         g["obs"][r], rphi[r], rq[r], g["loadings"][r] = y, phi, q, load
         g["patterns"].append(pat)
