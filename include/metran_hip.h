@@ -54,12 +54,18 @@ typedef enum mk_status {
 } mk_status;
 
 /* per-instance status bits written to mk_outputs.d_status */
-#define MK_FLAG_NONPOSITIVE_F 1u /* an innovation variance f <= 0 was met in the filter    */
+#define MK_FLAG_NONPOSITIVE_F 1u /* ERROR: an innovation variance f <= 0, or a NaN one, was met in the filter (anywhere in the
+                                    record, the warm-up included), or the filtered state ended NaN (a NaN x0, say, with every f
+                                    positive).  The instance's d_mle is then NaN -- never a finite number: the
+                                    reference's log f is NaN there (kalmanfilter.py:378) -- and its other outputs are unspecified */
 #define MK_FLAG_NOT_SPD 2u       /* ERROR: predicted covariance indefinite in the smoother (an LDL^T
                                     pivot < -1e-8); the smoothed moments of that instance are invalid */
 #define MK_FLAG_RANK_DEFICIENT 4u /* INFO: a pivot <= 0 was met and that null direction dropped, as
                                     numpy.linalg.pinv does in the reference (kalmanfilter.py:455): q_i = 0
-                                    for a series with communality 1 (metran.py:314-316).  Results valid. */
+                                    for a series with communality 1 (metran.py:314-316).  Results valid.
+                                    A NaN pivot sets NEITHER pivot bit, in every smoother (both comparisons are false; 1/d := 0):
+                                    NaN moments in give NaN moments out, and filtered moments that are NaN come from a filter
+                                    that has set MK_FLAG_NONPOSITIVE_F for the instance. */
 
 typedef struct mk_context mk_context; /* opaque; one per (process, device) */
 
@@ -301,7 +307,8 @@ MK_API int mk_lbfgs_update(mk_context *ctx, int64_t R, int64_t n, int64_t histor
 MK_API int mk_filter(mk_context *ctx, const mk_problem *prob, const mk_outputs *out);
 
 /* -2 log L only: mk_filter with every state output NULL (the solver's objective,
- * Metran.get_mle, metran/metran.py:605-622).  d_mle [B] required. */
+ * Metran.get_mle, metran/metran.py:605-622).  d_mle [B] required.  There is no status argument: an instance that would carry
+ * MK_FLAG_NONPOSITIVE_F (an innovation variance f <= 0 or NaN) returns a NaN d_mle, whatever the parity of its negative f's. */
 MK_API int mk_loglik(mk_context *ctx, const mk_problem *prob, double *d_mle);
 /* (When every instance shares ONE record -- n_records == 1, the solver's finite-difference points -- and
  * N+K <= 16, mk_loglik walks only the record's observed steps and applies the runs of empty steps in closed
@@ -372,6 +379,10 @@ MK_API int mk_loo(mk_context *ctx, const mk_problem *prob, double *d_work, int t
  * all three in the layout of prob->obs_time_major ([T, ndraws * n_instances, .] when set).  d_L0 [n_instances,n,n]: the lower
  * Cholesky factor of P0, NULL = identity (the default P0); the initial mean of x+ is zero whatever x0 is; the observation normals
  * are drawn only when prob->d_obsvar is set.  prob->d_x0, d_P0, d_scale, d_offset and warmup are not read.
+ *   INVALID parameters are not hidden: a NaN phi, a NaN or negative q or observation variance (the square root is NaN) make x+, y+
+ * and with them y* NaN at the cells they reach, observed ones included, and there is no status word.  A smoother takes a NaN y* for
+ * a MISSING cell, so a caller must treat a path whose y* is not finite at an observed cell as invalid before smoothing it
+ * (BatchedKalman.draw_smoothed sets MK_FLAG_NONPOSITIVE_F for the path and returns NaN draws).
  *   The caller then smooths y* with the EXISTING mk_filter_smooth on a derived problem of ndraws * n_instances instances and as
  * many records (d_obs = d_ystar; d_phi, d_q, d_loadings, d_obsvar, d_scale, d_offset, d_x0, d_P0 replicated per path) and adds the
  * unconditional part with mk_draw_combine, in place on the smoother's output (both arrays in the layout `time_major`):
@@ -401,7 +412,8 @@ MK_API int mk_draw_normals(mk_context *ctx, uint64_t seed, int64_t first_instanc
 
 /* kalmansmoother for B instances (kalmanfilter.py:403-476).  Reads out->d_F and out->d_Pf
  * (as written by mk_filter); predicted moments are recomputed from them (Phi diagonal), so
- * d_Xp/d_Pp are not read.  Writes d_S, d_Ps (either may be NULL), d_status. */
+ * d_Xp/d_Pp are not read.  Writes d_S, d_Ps (either may be NULL), d_status.  d_status is OVERWRITTEN (cleared on the context's
+ * stream, then the smoother's bits), as by mk_smooth_dense; only mk_filter_smooth keeps the filter's bits beside the smoother's. */
 MK_API int mk_smooth(mk_context *ctx, const mk_problem *prob, const mk_outputs *out);
 
 /* run_smoother (kalmanfilter.py:676-694): mk_filter then mk_smooth on the same stream. */

@@ -748,7 +748,9 @@ static int do_filter(mk_context *ctx, const mk_problem *p, const mk_outputs *o)
     return MK_OK;
 }
 
-static int do_smooth(mk_context *ctx, const mk_problem *p, const mk_outputs *o)
+// clear_status: the smoother kernels OR their bits into d_status -- behind mk_filter_smooth the filter's stay, called on its own mk_smooth
+// WRITES the word: it is cleared on the stream once every argument check has passed, right before the launch
+static int do_smooth(mk_context *ctx, const mk_problem *p, const mk_outputs *o, bool clear_status)
 {
     const int tape = tape_outputs(p, o);
     if (tape < 0) return tape;
@@ -821,6 +823,7 @@ static int do_smooth(mk_context *ctx, const mk_problem *p, const mk_outputs *o)
         ctx->variant[MK_VARIANT_KERNEL_FAMILY] == 0)
         return fail(MK_ERR_SHAPE, "the round-1 wide smoother (MK_VARIANT_WIDE_SMOOTHER 1) is built for N + K <= %d (got N=%lld, K=%lld)",
                     mk::wave_smoother_max_n, (long long)p->N, (long long)p->K);
+    if (clear_status && o->d_status) MK_HIP(hipMemsetAsync(o->d_status, 0, (size_t)p->n_instances * sizeof(uint32_t), ctx->stream));
     MK_HIP(dispatch_smoother(ctx, (int)p->N, (int)p->K, a, ctx->stream));
     MK_HIP(timing_stop(ctx, 1));
     return MK_OK;
@@ -855,7 +858,7 @@ MK_API int mk_smooth(mk_context *ctx, const mk_problem *p, const mk_outputs *o)
     MK_CTX(ctx);
     if (int rc = check_problem(p)) return rc;
     if (!o) return fail(MK_ERR_INVALID, "null mk_outputs");
-    return do_smooth(ctx, p, o);
+    return do_smooth(ctx, p, o, true);
 }
 
 MK_API int mk_smooth_dense(mk_context *ctx, int64_t B, int64_t T, int64_t n, const double *d_phi, const double *d_F,
@@ -885,6 +888,7 @@ MK_API int mk_smooth_dense(mk_context *ctx, int64_t B, int64_t T, int64_t n, con
     g.Xp = d_Xp;
     g.Pp = d_Pp;
     MK_HIP(generic_workspace(ctx, B, (int)n, &g.ws));
+    if (d_status) MK_HIP(hipMemsetAsync(d_status, 0, (size_t)B * sizeof(uint32_t), ctx->stream)); // the kernel ORs; this call writes
     MK_HIP(timing_start(ctx, 1));
     MK_HIP(mk::launch_smoother_generic(g, ctx->stream));
     MK_HIP(timing_stop(ctx, 1));
@@ -899,7 +903,7 @@ MK_API int mk_filter_smooth(mk_context *ctx, const mk_problem *p, const mk_outpu
     if ((o->flags & MK_OUT_VAR_ONLY) && !(o->flags & MK_OUT_TAPE) && (o->d_Xp || o->d_Pp))
         return fail(MK_ERR_INVALID, "MK_OUT_VAR_ONLY: d_Xp / d_Pp must be NULL (the filter writes the filtered record only)");
     if (int rc = do_filter(ctx, p, o)) return rc;
-    return do_smooth(ctx, p, o);
+    return do_smooth(ctx, p, o, false);
 }
 
 MK_API int mk_simulate(mk_context *ctx, int64_t B, int64_t RZ, int64_t T, int64_t N, int64_t n, const double *Z,

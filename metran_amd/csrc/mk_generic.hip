@@ -320,9 +320,9 @@ __global__ void __launch_bounds__(NT) smoother_generic_kernel(GenericSmootherArg
             const double piv = A[k * sa + k];
             double di = 0.0;
             if (piv > 0.0) di = gen_rcp(piv);
-            else {
+            else if (piv <= 0.0) {                     // (a NaN pivot sets neither bit, as in the specialised smoothers: metran_hip.h)
                 flags |= MK_FLAG_RANK_DEFICIENT;       // null direction dropped (the reference's pinv, :455)
-                if (piv < -1e-8 || !(piv == piv)) flags |= MK_FLAG_NOT_SPD;
+                if (piv < -1e-8) flags |= MK_FLAG_NOT_SPD;
             }
             if (tid == 0) dinv[k] = di;
             const int m = n - 1 - k, w = m + n, tot = m * w;

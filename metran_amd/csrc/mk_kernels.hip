@@ -584,9 +584,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 6
     }
     if (lead) {
         if (!BOOK) sum_det = fma((double)run_exp, kLn2, log(run_mant));
-        if (a.mle) a.mle[inst] = ((double)nobs * kLog2Pi + sum_det) + sum_sig; // :566
+        // an invalid model -- an innovation variance f <= 0, or a NaN one -- gets a NaN objective and the flag: the product of the f's
+        // loses the sign of an even number of negative ones, and v_min_f64 skips a NaN operand, but a NaN f makes every gain and with
+        // it the state NaN for good
+        const bool bad_f = !(fmin_seen > 0.0) || x != x;
+        if (a.mle) a.mle[inst] = bad_f ? __builtin_nan("") : ((double)nobs * kLog2Pi + sum_det) + sum_sig; // :566
         if (a.sigmacount) a.sigmacount[inst] = sc;
-        if (a.status) a.status[inst] = (fmin_seen > 0.0) ? 0u : MK_FLAG_NONPOSITIVE_F; // NaN f also flags
+        if (a.status) a.status[inst] = bad_f ? MK_FLAG_NONPOSITIVE_F : 0u;
     }
 }
 
@@ -1707,8 +1711,9 @@ __global__ void __launch_bounds__(256) loglik_sparse_kernel(SparseArgs a)
     }
     if (lead) {
         const double sum_det = fma((double)run_exp, kLn2, log(run_mant));
-        if (a.mle) a.mle[inst] = ((double)nobs * kLog2Pi + sum_det) + sum_sig;
-        if (a.status) a.status[inst] = (fmin_seen > 0.0) ? 0u : MK_FLAG_NONPOSITIVE_F;
+        const bool bad_f = !(fmin_seen > 0.0) || x != x; // as in filter_kernel: f <= 0 or NaN -> NaN objective and the flag
+        if (a.mle) a.mle[inst] = bad_f ? __builtin_nan("") : ((double)nobs * kLog2Pi + sum_det) + sum_sig;
+        if (a.status) a.status[inst] = bad_f ? MK_FLAG_NONPOSITIVE_F : 0u;
         if (REC && a.sigmacount) a.sigmacount[inst] = cnt;
     }
 }

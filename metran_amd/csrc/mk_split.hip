@@ -673,9 +673,10 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     }
     if (l == 0) {
         if (!BOOK) sum_det = fma((double)run_exp, kLn2, log(run_mant));
-        if (a.mle) a.mle[inst] = ((double)nobs * kLog2Pi + sum_det) + sum_sig; // :566
+        const bool bad_f = !(fmin_seen > 0.0) || x != x; // as in filter_kernel (mk_kernels.hip): f <= 0 or NaN -> NaN objective and the flag
+        if (a.mle) a.mle[inst] = bad_f ? __builtin_nan("") : ((double)nobs * kLog2Pi + sum_det) + sum_sig; // :566
         if (a.sigmacount) a.sigmacount[inst] = sc;
-        if (a.status) a.status[inst] = (fmin_seen > 0.0) ? 0u : MK_FLAG_NONPOSITIVE_F; // NaN f also flags
+        if (a.status) a.status[inst] = bad_f ? MK_FLAG_NONPOSITIVE_F : 0u;
     }
 }
 
@@ -1253,9 +1254,10 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     }
     if (l == 0) {
         if (!BOOK) sum_det = fma((double)run_exp, kLn2, log(run_mant));
-        if (a.mle) a.mle[inst] = ((double)nobs * kLog2Pi + sum_det) + sum_sig; // :566
+        const bool bad_f = !(fmin_seen > 0.0) || xo != xo; // as in filter_kernel (mk_kernels.hip): f <= 0 or NaN -> NaN objective and the flag
+        if (a.mle) a.mle[inst] = bad_f ? __builtin_nan("") : ((double)nobs * kLog2Pi + sum_det) + sum_sig; // :566
         if (a.sigmacount) a.sigmacount[inst] = sc;
-        if (a.status) a.status[inst] = (fmin_seen > 0.0) ? 0u : MK_FLAG_NONPOSITIVE_F; // NaN f also flags
+        if (a.status) a.status[inst] = bad_f ? MK_FLAG_NONPOSITIVE_F : 0u;
     }
 }
 

@@ -825,7 +825,8 @@ class BatchedKalman:
         observation variance a series draw is the observation.  ``antithetic``: draws 2k and 2k + 1 mirror each other around
         the smoothed mean.  Draws run in chunks sized by the free device memory (``chunk=`` forces a size); the result does not
         depend on the chunk size.  ``first_draw`` / ``first_instance`` number this call's draws / instances within a larger
-        ensemble.  Returns ``{"draws": [S,B,T,N] or [S,B,T,n], "status": [S,B]}``."""
+        ensemble.  Returns ``{"draws": [S,B,T,N] or [S,B,T,n], "status": [S,B]}``; a path whose parameters are invalid (its
+        simulated record is not finite at an observed cell) carries ``FLAG_NONPOSITIVE_F`` and NaN draws."""
         torch = _torch()
         if what not in ("series", "states"):
             raise ValueError("what must be 'series' or 'states'")
@@ -854,10 +855,15 @@ class BatchedKalman:
         sub = self._draw_sub_engine(B)
         rec = torch.arange(B, device=self.device) % self.R
         rep = lambda a, c, *ones: None if a is None else a.repeat(c, *ones)  # noqa: E731
+        seen = torch.isfinite(self.obs)[rec]             # [B,T,N]: the observed cells of every instance's record
         res = out = None
         for s0 in range(0, S, chunk):
             c = min(chunk, S - s0)
             ystar, zx, xp = self._draw_perturb(prob, B, c, seed, first_instance, first_draw + s0, antithetic, L0, series, not series)
+            # an OBSERVED cell whose y* is not finite: the path's parameters are invalid (a NaN persistence, a negative or NaN q or
+            # observation variance: mk_draw_perturb).  The smoothing pass would take the cell for a missing one and never meet them,
+            # so the path is flagged here (MK_FLAG_NONPOSITIVE_F, the filter's error bit) and its draws are NaN
+            lost = (seen.repeat(c, 1, 1) & ~torch.isfinite(ystar)).flatten(1).any(1)
             # the derived problem: one record per path, this engine's CURRENT loadings / variances / scaling replicated over the draws
             sub._adopt_records(ystar, rep(self.loadings[rec], c, 1, 1), rep(None if self.obsvar is None else self.obsvar[rec], c, 1),
                                rep(None if self.scale is None else self.scale[rec], c, 1),
@@ -877,8 +883,8 @@ class BatchedKalman:
             self._bind_stream()
             check(self._L.mk_draw_combine(self._ctx, ctypes.byref(prob), c, 0 if series else 1, 1 if self.time_major else 0,
                                           self._p(zx if series else xp), self._p(out)))
-            draws[s0:s0 + c] = out.unflatten(0, (c, B))
-            status[s0:s0 + c] = res["status"].view(c, B)
+            draws[s0:s0 + c] = out.masked_fill(lost[:, None, None], float("nan")).unflatten(0, (c, B))
+            status[s0:s0 + c] = (res["status"] | lost.to(torch.int32) * FLAG_NONPOSITIVE_F).view(c, B)
             sub.obs = None   # y* of this chunk is done with
         return {"draws": draws, "status": status}
 
