@@ -368,6 +368,42 @@ MK_API int64_t mk_loo_work_stride(int64_t N, int64_t K);
 MK_API int mk_loo(mk_context *ctx, const mk_problem *prob, double *d_work, int time_major, double *d_loo_means,
                   double *d_loo_vars, uint32_t *d_status);
 
+/* One-step-ahead INNOVATIONS of every observed cell and the one-step-ahead forecast of every series (the quantities the filter
+ * forms in every scalar update, kalmanfilter.py:341-378, and folds into sigmas[t] = sum v^2/f, detfs[t] = sum log f).  For step t,
+ * after the prediction from the filtered moments of step t - 1 (x0 / P0 at t = 0) and with the observed series of the step taken
+ * in ASCENDING order, the update of series j has
+ *     d_v[b,t,j] = y_tj - z_j x,   d_f[b,t,j] = z_j P z_j' + R_j      (x, P: the state after the updates of the observed series < j)
+ * in the filter's own units (no scale / offset), NaN at a cell that is not observed.  The standardised one-step-ahead prediction
+ * error is e = v / sqrt(f): under the model the e of all observed cells are independent N(0,1).  v and f DEPEND ON THE ORDER of the
+ * series (cell (t, j) is predicted from the past and from the cells (t, < j)); the MARGINAL forecast, from the past alone, does not:
+ *     d_pred_means[b,t,j] = (z_j x_{t|t-1}) * scale + offset,   d_pred_vars[b,t,j] = max(z_j P_{t|t-1} z_j' + R_j, 0) * scale^2
+ * for EVERY series, observed or not (scale / offset: mk_problem.d_scale / d_offset).  For the first observed series of a step
+ * v = y - pred_mean and f = pred_var (unscaled).  All four are [B,T,N], or [T,B,N] with time_major; any of them may be NULL (with
+ * d_v and d_f both NULL the updates are not run), not all four.  Two launches: the recording forward pass of mk_loglik_grad
+ * into d_work -- n_instances * T * mk_innovations_work_stride(N, K) doubles, filtered full-square records -- and innov_step_kernel,
+ * one (instance, step) per lane group: step t needs the record of step t - 1 only.  prob->warmup is ignored; d_status (may be
+ * NULL) receives the filter's MK_FLAG_* bits -- the outputs of an instance with MK_FLAG_NONPOSITIVE_F are not meaningful.
+ *   Served: every supported shape with N + K <= 64, specialised or not, and under either kernel family: the size-generic
+ * filter writes the same filtered-only full-square records (the transpose of the specialised kernels' image, equal up to the
+ * rounding-level asymmetry of the rank-one updates).  mk_innovations_work_stride returns mk_record_stride(N + K) for those and 0
+ * otherwise; mk_innovations then fails with MK_ERR_SHAPE.  MK_ERR_INVALID (no launch) for a missing d_work, for all four outputs
+ * NULL, and for a buffer that is larger than the allocation it points into.  The step kernel is timed in the smoother slot of
+ * mk_last_kernel_ms / mk_kernel_ms_totals.
+ *
+ * mk_innovation_stats: the portmanteau (Ljung-Box) statistics of e per (instance, series).  With t_1 < ... < t_m the cells of
+ * series j that have finite v, finite f > 0 and t >= t_first, and e_i = v / sqrt(f) at t_i:
+ *     mean = sum e_i / m,   c_l = sum_{i=1}^{m-l} (e_i - mean)(e_{i+l} - mean) / m,   r_l = c_l / c_0,
+ *     Q = m (m + 2) sum_{l=1}^{nlags} r_l^2 / (m - l)
+ * -- lags count successive VALID cells of the series, not calendar steps.  d_stats [B,N,4+nlags] = [m, mean, c_0, Q, r_1 .. r_nlags],
+ * 1 <= nlags <= 32; r_l and Q are NaN when m <= nlags or c_0 = 0, mean and c_0 when m = 0.  d_v / d_f as written by mk_innovations
+ * ([B,T,N], or [T,B,N] with time_major).  Every sum is taken in an order fixed by T and the series' own cells: a series' statistics
+ * are bit-identical whatever the batch around it.  Under the model Q is approximately chi-square with nlags degrees of freedom. */
+MK_API int64_t mk_innovations_work_stride(int64_t N, int64_t K);
+MK_API int mk_innovations(mk_context *ctx, const mk_problem *prob, double *d_work, int time_major, double *d_v, double *d_f,
+                          double *d_pred_means, double *d_pred_vars, uint32_t *d_status);
+MK_API int mk_innovation_stats(mk_context *ctx, int64_t B, int64_t T, int64_t N, int time_major, int64_t t_first, int64_t nlags,
+                               const double *d_v, const double *d_f, double *d_stats);
+
 /* Posterior DRAWS of the states and of the projected series: the simulation smoother by mean correction (Durbin & Koopman 2002,
  * Biometrika 89:603-616).  For the model the filter implements (seqkalmanfilter, metran/kalmanfilter.py:315-333:
  * x_{-1} ~ N(x0, P0), x_t = phi o x_{t-1} + w_t, y_t = [I | Gamma] x_t + e_t) and path id = s * n_instances + i (draw s of instance i,

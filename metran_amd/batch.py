@@ -145,7 +145,8 @@ class MetranBatch:
     def _run(self, kind, alpha):
         """kind: "project" (filter + projecting smoother: sim_means/sim_vars in ORIGINAL units), "smoother" (filter +
         smoother with the state moments), "filter" (filter with the filtered moments), "loo" (leave-one-out predictions
-        loo_means/loo_vars in ORIGINAL units).  One cached result per kind,
+        loo_means/loo_vars in ORIGINAL units), "innov" (one-step-ahead innovations v/f in standardised units and forecasts
+        pred_mean/pred_var in ORIGINAL units).  One cached result per kind,
         valid for the parameter set it was computed with (metran.py:978-989 keeps one too)."""
         import torch
 
@@ -168,6 +169,9 @@ class MetranBatch:
         elif kind == "loo":
             self.kf.set_scaling(self._std, self._mean)
             out = self.kf.loo_predict(phi, q)
+        elif kind == "innov":
+            self.kf.set_scaling(self._std, self._mean)
+            out = self.kf.innovations(phi, q)
         else:
             raise ValueError(kind)
         check_status(out["status"], "MetranBatch(%s)" % kind)
@@ -250,6 +254,59 @@ class MetranBatch:
         means, variances = self._loo(alpha, True)
         obs = self.kf.obs
         return torch.where(torch.isfinite(obs), (obs - means) / torch.sqrt(variances), torch.full_like(means, float("nan")))
+
+    # ------------------------------------------------------------------ one-step-ahead innovations (model adequacy)
+    def get_innovations(self, alpha=None, standardized=True):
+        """One-step-ahead prediction errors ``[R,T,N]`` of every observed cell (NaN elsewhere).  ``standardized=True``:
+        ``e = v / sqrt(f)``, independent N(0,1) under the fitted model -- the same number in standardised and original units.
+        ``standardized=False``: the pair ``(v, f)`` of raw innovations and their variances, in the units the filter runs in
+        (the standardised series).  Cell (t, j) is predicted from the past and from the series before j of the same step (the
+        filter's sequential updates), so ``v`` and ``f`` -- not the whiteness of ``e`` -- depend on the order of the series."""
+        import torch
+
+        out = self._run("innov", alpha)
+        if not standardized:
+            return out["v"], out["f"]
+        return out["v"] / torch.sqrt(out["f"])
+
+    def get_prediction(self, r, name, alpha=None, ci=0.05, standardized=False):
+        """The ONE-STEP-AHEAD counterpart of ``get_simulation``: DataFrame (``mean``, ``lower``, ``upper``) of the forecast of
+        series ``name`` of model ``r`` at every step from the observations before that step alone -- the band is that of the
+        OBSERVATION (projected state variance plus observation variance), defined at every step, observed or not, and
+        independent of the order of the series.  ``ci=None`` returns the mean Series."""
+        j = self._series(r, name)
+        out = self._run("innov", alpha)  # original units
+        means, variances = out["pred_mean"], out["pred_var"]
+        if standardized:
+            means = (means - self._mean[:, None, :]) / self._std[:, None, :]
+            variances = variances / (self._std * self._std)[:, None, :]
+        L = int(self.batch.lengths[r])
+        sim = self.batch.frame(r, means[r].cpu().numpy()).iloc[:L, j]
+        return self._band(sim, self.batch.frame(r, variances[r].cpu().numpy()).iloc[:L, j] if ci is not None else None, ci)
+
+    def test_whiteness(self, alpha=None, nlags=10, t_first=1):
+        """Portmanteau (Ljung-Box) check of every series' standardised innovations: DataFrame indexed (model, series) with
+        ``nobs`` (cells used: observed, ``t >= t_first``), ``mean`` and ``var`` of ``e``, ``Q = m (m + 2) sum_l r_l^2 / (m - l)``,
+        ``pvalue = chi2.sf(Q, nlags)`` and the autocorrelations ``r1 .. r<nlags>``.  Lags count successive OBSERVED cells of the
+        series, not calendar steps (the portmanteau test on the non-missing values; Metran's records are sparse).  A small
+        p-value says the model's noise is not white: the model is not adequate for that series.  NO degrees of freedom are
+        subtracted for the estimated parameters (the textbook correction for a fitted ARMA model would use ``nlags - p``): the
+        p-value is on the generous side for a calibrated model.  ``t_first=1`` leaves out the first step, whose prediction is
+        the initial state's.  NaN where a series has no more than ``nlags`` cells or does not vary."""
+        from pandas import DataFrame, MultiIndex
+        from scipy.stats import chi2
+
+        nlags = int(nlags)
+        out = self._run("innov", alpha)
+        stats = self.kf.innovation_stats(out["v"], out["f"], nlags=nlags, t_first=t_first).cpu().numpy()
+        index = MultiIndex.from_tuples([(r + self.shard[0], name) for r in range(self.R) for name in self.batch.names[r]],
+                                       names=["model", "series"])
+        flat = stats.reshape(self.R * self.N, 4 + nlags)
+        frame = DataFrame({"nobs": flat[:, 0].astype(np.int64), "mean": flat[:, 1], "var": flat[:, 2], "Q": flat[:, 3],
+                           "pvalue": chi2.sf(flat[:, 3], nlags)}, index=index)
+        for l in range(1, nlags + 1):
+            frame["r%d" % l] = flat[:, 3 + l]
+        return frame
 
     # ------------------------------------------------------------------ posterior draws (simulation smoother)
     def _draws(self, what, ndraws, seed, alpha, antithetic):

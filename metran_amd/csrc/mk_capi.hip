@@ -12,6 +12,7 @@
 #include <new>
 
 #include "draw_kernels.h"
+#include "innov_kernels.h"
 #include "mk_generic.h"
 #include "mk_internal.h"
 #include "mk_lbfgs.h"
@@ -1258,6 +1259,103 @@ MK_API int mk_draw_normals(mk_context *ctx, uint64_t seed, int64_t first_instanc
     a.raw = raw != 0;
     a.out = d_out;
     MK_HIP(mk::launch_draw_normals(a, ctx->stream));
+    return MK_OK;
+}
+
+// ---- one-step-ahead innovations and their whiteness statistics (innov_kernels.hip) ----
+MK_API int64_t mk_innovations_work_stride(int64_t N, int64_t K)
+{
+    if (N < 1 || K < 1 || N + K > mk::innov_max_states || !mk_shape_supported(N, K)) return 0;
+    return mk::record_stride((int)(N + K));
+}
+
+MK_API int mk_innovations(mk_context *ctx, const mk_problem *p, double *d_work, int time_major, double *d_v, double *d_f,
+                          double *d_pred_means, double *d_pred_vars, uint32_t *d_status)
+{
+    MK_CTX(ctx);
+    if (int rc = check_problem(p)) return rc;
+    if (!d_work) return fail(MK_ERR_INVALID, "mk_innovations: d_work is required");
+    if (!d_v && !d_f && !d_pred_means && !d_pred_vars)
+        return fail(MK_ERR_INVALID, "mk_innovations: nothing to write, give one of d_v, d_f, d_pred_means, d_pred_vars");
+    if (!p->d_obs || !p->d_loadings) return fail(MK_ERR_INVALID, "d_obs and d_loadings are required");
+    const int64_t ws = mk_innovations_work_stride(p->N, p->K);
+    if (!ws)
+        return fail(MK_ERR_SHAPE, "mk_innovations serves N + K <= %d states (got N=%lld, K=%lld)", mk::innov_max_states, (long long)p->N,
+                    (long long)p->K);
+    const int64_t n = p->N + p->K, cells = p->n_instances * p->T * p->N;
+    const draw_buffer bufs[5] = {{d_work, p->n_instances * p->T * ws, "d_work (n_instances * T * mk_innovations_work_stride(N, K) doubles)"},
+                                 {d_v, cells, "d_v (n_instances * T * N doubles)"},
+                                 {d_f, cells, "d_f (n_instances * T * N doubles)"},
+                                 {d_pred_means, cells, "d_pred_means (n_instances * T * N doubles)"},
+                                 {d_pred_vars, cells, "d_pred_vars (n_instances * T * N doubles)"}};
+    if (int rc = draw_buffers_fit("mk_innovations", bufs, 5)) return rc;
+    // the recording forward pass of mk_loglik_grad: filtered records only (+ the per-step bookkeeping in the record pads)
+    mk_outputs o;
+    memset(&o, 0, sizeof(o));
+    o.d_status = d_status;
+    o.d_F = d_work;
+    o.d_Pf = d_work + n;
+    o.d_sigmas = d_work + n + n * n;
+    o.d_detfs = o.d_sigmas + 1;
+    o.time_major = time_major;
+    o.record_stride = ws;
+    if (int rc = do_filter(ctx, p, &o)) return rc;
+    mk::InnovArgs a;
+    memset(&a, 0, sizeof(a));
+    a.B = p->n_instances;
+    a.R = p->n_records;
+    a.T = p->T;
+    a.N = (int)p->N;
+    a.K = (int)p->K;
+    a.bs = time_major ? 1 : p->T;
+    a.ts = time_major ? p->n_instances : 1;
+    a.rs = ws;
+    a.obs_bs = p->obs_time_major ? 1 : p->T;
+    a.obs_ts = p->obs_time_major ? p->n_records : 1;
+    a.obs = p->d_obs;
+    a.phi = p->d_phi;
+    a.q = p->d_q;
+    a.loadings = p->d_loadings;
+    a.obsvar = p->d_obsvar;
+    a.x0 = p->d_x0;
+    a.P0 = p->d_P0;
+    a.scale = p->d_scale;
+    a.offset = p->d_offset;
+    a.F = d_work;
+    a.v = d_v;
+    a.f = d_f;
+    a.pred_mean = d_pred_means;
+    a.pred_var = d_pred_vars;
+    MK_HIP(timing_start(ctx, 1));
+    MK_HIP(mk::launch_innov_step(a, ctx->stream));
+    MK_HIP(timing_stop(ctx, 1)); // reported in the smoother slot of mk_last_kernel_ms / mk_kernel_ms_totals
+    return MK_OK;
+}
+
+MK_API int mk_innovation_stats(mk_context *ctx, int64_t B, int64_t T, int64_t N, int time_major, int64_t t_first, int64_t nlags,
+                               const double *d_v, const double *d_f, double *d_stats)
+{
+    MK_CTX(ctx);
+    if (B < 1 || T < 1 || N < 1 || t_first < 0 || nlags < 1 || nlags > mk::innov_max_lags)
+        return fail(MK_ERR_INVALID, "mk_innovation_stats: need B, T, N >= 1, t_first >= 0 and 1 <= nlags <= %d", mk::innov_max_lags);
+    if (!d_v || !d_f || !d_stats) return fail(MK_ERR_INVALID, "mk_innovation_stats: d_v, d_f and d_stats are required");
+    const draw_buffer bufs[3] = {{d_v, B * T * N, "d_v (B * T * N doubles)"},
+                                 {d_f, B * T * N, "d_f (B * T * N doubles)"},
+                                 {d_stats, B * N * (4 + nlags), "d_stats (B * N * (4 + nlags) doubles)"}};
+    if (int rc = draw_buffers_fit("mk_innovation_stats", bufs, 3)) return rc;
+    mk::InnovStatsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.B = B;
+    a.T = T;
+    a.N = (int)N;
+    a.L = (int)nlags;
+    a.bs = time_major ? 1 : T;
+    a.ts = time_major ? B : 1;
+    a.t_first = t_first;
+    a.v = d_v;
+    a.f = d_f;
+    a.stats = d_stats;
+    MK_HIP(mk::launch_innov_stats(a, ctx->stream));
     return MK_OK;
 }
 

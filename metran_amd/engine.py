@@ -746,6 +746,83 @@ class BatchedKalman:
                              self._p(res["loo_means"]), self._p(res["loo_vars"]), self._p(res["status"])))
         return res
 
+    # ------------------------------------------------------------------ one-step-ahead innovations
+    _INNOVATION_OUTPUTS = ("v", "f", "pred_mean", "pred_var")
+
+    @property
+    def innovations_supported(self):
+        """True when ``innovations`` serves this engine's shape (C ABI ``mk_innovations_work_stride`` > 0): N + K <= 64,
+        specialised or size-generic kernels alike."""
+        return self.loadings is not None and int(self._L.mk_innovations_work_stride(self.N, self.K)) > 0
+
+    def _innovations_stride(self):
+        if not self.innovations_supported:
+            raise MetranHipError("innovations serve shapes with N + K <= 64; (N=%s, K=%s) is not one" % (self.N, getattr(self, "K", None)))
+        return int(self._L.mk_innovations_work_stride(self.N, self.K))
+
+    def alloc_innovations(self, B, outputs=_INNOVATION_OUTPUTS):
+        """Buffers of ``innovations`` for B instances (the forward pass's workspace + the outputs asked for), for callers that
+        run it repeatedly (pass them back as ``buffers=``)."""
+        torch = _torch()
+        res = {"_work": self._empty_bt(B, self.T, self._innovations_stride()),
+               "status": torch.zeros(B, dtype=torch.int32, device=self.device)}
+        for key in outputs:
+            res[key] = self._empty_bt(B, self.T, self.N)
+        return res
+
+    def innovations(self, phi, q, x0=None, P0=None, buffers=None, outputs=_INNOVATION_OUTPUTS):
+        """ONE-STEP-AHEAD innovations for B instances (C ABI ``mk_innovations``): ``v[b,t,j]`` and ``f[b,t,j]`` are the innovation
+        and its variance of the scalar update of the observed cell (t, j) -- the cell predicted from the past and from the series
+        < j of the same step, so they depend on the order of the series; ``e = v / sqrt(f)`` is independent N(0,1) under the
+        model -- NaN where a cell is not observed; ``pred_mean[b,t,j]`` / ``pred_var[b,t,j]`` are the forecast of EVERY series from
+        the past alone (which does not depend on the order), in the units of ``set_scaling`` and with the observation variance
+        included.  ``outputs``: which of the four to compute.  Returns a dict with those ``[B,T,N]`` tensors and ``status`` (the
+        filter's MK_FLAG_* bits); the rows of an instance whose status carries ``FLAG_NONPOSITIVE_F`` are NaN."""
+        outputs = tuple(outputs)
+        if not outputs or any(k not in self._INNOVATION_OUTPUTS for k in outputs):
+            raise ValueError("outputs must be a non-empty subset of %s" % (self._INNOVATION_OUTPUTS,))
+        stride = self._innovations_stride()
+        prob, keep, B = self._problem(phi, q, 0, x0, P0)
+        res = buffers if buffers is not None else self.alloc_innovations(B, outputs)
+        for key, tail in (("_work", stride),) + tuple((k, self.N) for k in outputs):
+            t = res.get(key)
+            if t is None or tuple(t.shape) != (B, self.T, tail) or self._layout(t) is not t:
+                raise ValueError("buffers[%r] must be a [%d,%d,%d] tensor in the engine's layout (alloc_innovations)"
+                                 % (key, B, self.T, tail))
+        ptr = {k: self._p(res[k]) if k in outputs else None for k in self._INNOVATION_OUTPUTS}
+        self._bind_stream()
+        check(self._L.mk_innovations(self._ctx, ctypes.byref(prob), self._p(res["_work"]), 1 if self.time_major else 0,
+                                     ptr["v"], ptr["f"], ptr["pred_mean"], ptr["pred_var"], self._p(res["status"])))
+        bad = (res["status"] & FLAG_NONPOSITIVE_F) != 0
+        for k in outputs:
+            res[k].masked_fill_(bad[:, None, None], float("nan"))
+        return res
+
+    def innovation_stats(self, v, f, nlags=10, t_first=0):
+        """Whiteness statistics of the standardised innovations ``e = v / sqrt(f)`` per (instance, series) (C ABI
+        ``mk_innovation_stats``): over the cells with finite ``v``, finite ``f > 0`` and ``t >= t_first``, in time order, the
+        count ``m``, the mean, the variance ``c_0`` (divisor m), the autocorrelations ``r_1 .. r_nlags`` at lags counted in
+        successive VALID cells (not calendar steps) and the Ljung-Box statistic ``Q = m (m + 2) sum r_l^2 / (m - l)``.  ``v``,
+        ``f``: ``[B,T,N]`` tensors in the engine's layout (as ``innovations`` returns them).  Returns ``[B,N,4+nlags]`` =
+        ``[m, mean, c_0, Q, r_1 .. r_nlags]``; ``r_l`` and ``Q`` are NaN when ``m <= nlags`` or ``c_0 = 0``."""
+        torch = _torch()
+        nlags, t_first = int(nlags), int(t_first)
+        if not 1 <= nlags <= 32:
+            raise ValueError("nlags must be in 1..32")
+        if t_first < 0:
+            raise ValueError("t_first must be >= 0")
+        if v.ndim != 3 or tuple(v.shape) != tuple(f.shape):
+            raise ValueError("v and f must be [B,T,N] tensors of one shape")
+        for name, t in (("v", v), ("f", f)):
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.device == self.device and self._layout(t) is t):
+                raise ValueError("%s must be a float64 tensor on %s in the engine's layout" % (name, self.device))
+        B, T, N = (int(s) for s in v.shape)
+        stats = torch.empty((B, N, 4 + nlags), dtype=torch.float64, device=self.device)
+        self._bind_stream()
+        check(self._L.mk_innovation_stats(self._ctx, B, T, N, 1 if self.time_major else 0, t_first, nlags, self._p(v), self._p(f),
+                                          self._p(stats)))
+        return stats
+
     # ------------------------------------------------------------------ posterior draws (simulation smoother)
     def _draw_perturb(self, prob, B, ndraws, seed, first_instance, first_draw, antithetic, L0, want_zx, want_x):
         """``mk_draw_perturb`` for ``ndraws`` draws of the B instances of ``prob``: ``(ystar, zxplus or None, xplus or None)``,
