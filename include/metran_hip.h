@@ -368,6 +368,27 @@ MK_API int64_t mk_loo_work_stride(int64_t N, int64_t K);
 MK_API int mk_loo(mk_context *ctx, const mk_problem *prob, double *d_work, int time_major, double *d_loo_means,
                   double *d_loo_vars, uint32_t *d_status);
 
+/* Smoothed STATE DISTURBANCES and the auxiliary residuals of the state equation (Harvey & Koopman 1992; statsmodels'
+ * smoothed_state_disturbance, KFAS' rstandard(type = "state")): did the state equation x_t = phi o x_{t-1} + eta_t fail somewhere,
+ * in which component and when -- a step change in one series' own state, a shift of a common factor.  The backward walk of the
+ * adjoint gradient, run with unit weight on every step, carries the Durbin-Koopman pair (r_t, N_t) of the state equation; between
+ * the updates of step t and the pull-back through Phi it writes, for every state i of every step (observed or not; t = 0 is the
+ * disturbance between the initial state and the first prediction),
+ *     d_r[b,t,i] = r_t,i,   d_ninfo[b,t,i] = N_t,ii   (a negative value from rounding is stored as 0)
+ * from which     E[eta_t,i | Y] = q_i r_t,i,   Var[eta_t,i | Y] = q_i - q_i^2 N_t,ii,   u_t,i = r_t,i / sqrt(N_t,ii)
+ * (u: the standardised auxiliary residual, unit spread under the model; q_i N_t,ii in [0,1] is the share of the disturbance's
+ * variance that the data determine -- 0 behind the last observation and for a state with q_i = 0).  The RAW pair is written so that
+ * u is never formed from a difference.  [B,T,N+K], or [T,B,N+K] with time_major.  Two launches: the recording forward pass of
+ * mk_loglik_grad into d_work -- n_instances * T * mk_disturbance_work_stride(N, K) doubles, filtered full-square records -- and one
+ * backward walk (adjoint_kernel for N + K <= 16, adjoint_wide_kernel in its recompute form for 16 < N + K <= 64, each in its
+ * disturbance mode).  prob->warmup is ignored; d_status (may be NULL) receives the filter's MK_FLAG_* bits.
+ * mk_disturbance_work_stride returns mk_record_stride(N + K) for a specialised shape with N + K <= 64 and 0 otherwise;
+ * mk_disturbances then fails with MK_ERR_SHAPE, as it does under the size-generic kernel family, and with MK_ERR_INVALID (no
+ * launch) for a missing buffer and for one that is larger than the allocation it points into. */
+MK_API int64_t mk_disturbance_work_stride(int64_t N, int64_t K);
+MK_API int mk_disturbances(mk_context *ctx, const mk_problem *prob, double *d_work, int time_major, double *d_r, double *d_ninfo,
+                           uint32_t *d_status);
+
 /* One-step-ahead INNOVATIONS of every observed cell and the one-step-ahead forecast of every series (the quantities the filter
  * forms in every scalar update, kalmanfilter.py:341-378, and folds into sigmas[t] = sum v^2/f, detfs[t] = sum log f).  For step t,
  * after the prediction from the filtered moments of step t - 1 (x0 / P0 at t = 0) and with the observed series of the step taken

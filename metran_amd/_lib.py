@@ -131,6 +131,8 @@ API = {
                               c_void_p, c_void_p]),
     "mk_loo_work_stride": (c_int64, [c_int64, c_int64]),
     "mk_loo": (c_int, [c_void_p, POINTER(Problem), c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "mk_disturbance_work_stride": (c_int64, [c_int64, c_int64]),
+    "mk_disturbances": (c_int, [c_void_p, POINTER(Problem), c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "mk_innovations_work_stride": (c_int64, [c_int64, c_int64]),
     "mk_innovations": (c_int, [c_void_p, POINTER(Problem), c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mk_innovation_stats": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),

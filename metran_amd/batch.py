@@ -10,6 +10,7 @@ number comes from the HIP kernels:
     simulate_smoothed        ->  filter + projecting smoother (get_simulated_means / _variances)
     loo_predict              ->  leave-one-out predictions of every observation (get_loo_simulation, get_deletion_residuals)
     smooth_state_variances   ->  state means / variances / decomposition
+    disturbances             ->  smoothed state disturbances and auxiliary residuals (get_auxiliary_residuals, screen_breaks)
 
 Results of the last filter / smoother run are cached per parameter set, like ``Metran._run_kalman`` does
 (metran.py:963-989): asking for another series, the variances after the means, or the decomposition after the
@@ -146,7 +147,8 @@ class MetranBatch:
         """kind: "project" (filter + projecting smoother: sim_means/sim_vars in ORIGINAL units), "smoother" (filter +
         smoother with the state moments), "filter" (filter with the filtered moments), "loo" (leave-one-out predictions
         loo_means/loo_vars in ORIGINAL units), "innov" (one-step-ahead innovations v/f in standardised units and forecasts
-        pred_mean/pred_var in ORIGINAL units).  One cached result per kind,
+        pred_mean/pred_var in ORIGINAL units), "dist" (the backward pair r/ninfo of the state disturbances, with the q they were
+        computed for).  One cached result per kind,
         valid for the parameter set it was computed with (metran.py:978-989 keeps one too)."""
         import torch
 
@@ -172,6 +174,9 @@ class MetranBatch:
         elif kind == "innov":
             self.kf.set_scaling(self._std, self._mean)
             out = self.kf.innovations(phi, q)
+        elif kind == "dist":
+            out = dict(self.kf.disturbances(phi, q))
+            out["q"] = q
         else:
             raise ValueError(kind)
         check_status(out["status"], "MetranBatch(%s)" % kind)
@@ -307,6 +312,75 @@ class MetranBatch:
         for l in range(1, nlags + 1):
             frame["r%d" % l] = flat[:, 3 + l]
         return frame
+
+    # ------------------------------------------------------------------ state disturbances (break detection)
+    def get_state_disturbances(self, alpha=None):
+        """Smoothed disturbances of the state equation x_t = phi o x_{t-1} + eta_t: ``(mean, variance)`` ``[R,T,N+K]`` of
+        ``eta_t`` given ALL data (statsmodels' ``smoothed_state_disturbance`` and its variance), in the filter's units.  With the
+        backward pair ``(r, N)`` of ``BatchedKalman.disturbances``: ``mean = q r`` and ``variance = q - q^2 N_ii`` (clipped at 0).
+        Row t = 0 is the disturbance between the initial state and the first prediction; padding steps are included."""
+        out = self._run("dist", alpha)
+        q = out["q"][:, None, :]
+        return q * out["r"], (q - q * q * out["ninfo"]).clamp_min(0.0)
+
+    def get_auxiliary_residuals(self, alpha=None, min_information=1e-6):
+        """Auxiliary residuals of the state equation ``[R,T,N+K]`` (Harvey & Koopman 1992; KFAS ``rstandard(type = "state")``):
+        ``u = r / sqrt(N_ii)``, the smoothed disturbance over its own standard deviation -- formed from the kernel's raw pair,
+        never from a difference.  Under the model every ``u`` has unit spread (neighbouring ones are correlated); a large
+        magnitude at (t, i) says that state i moved at step t by more than its noise allows: a level shift in a series' own
+        state, a shift of a common factor.  NaN beyond a model's own length, and where ``q_i N_ii < min_information``:
+        ``q_i N_ii`` in [0,1] is the share of the disturbance's variance that the data determine -- 0 behind the last
+        observation and for a state with q = 0 -- and a ratio of two vanishing numbers is not a residual.  The threshold is a
+        stated policy, not a measurement."""
+        import torch
+
+        out = self._run("dist", alpha)
+        r, ninfo = out["r"], out["ninfo"]
+        q = out["q"][:, None, :]
+        lengths = torch.as_tensor(np.asarray(self.batch.lengths), device=r.device)
+        inside = torch.arange(r.shape[1], device=r.device)[None, :, None] < lengths[:, None, None]
+        ok = inside & (q * ninfo >= float(min_information))
+        return torch.where(ok, r / torch.sqrt(ninfo), torch.full_like(r, float("nan")))
+
+    def get_state_disturbance(self, r, i, alpha=None, ci=0.05):
+        """The smoothed disturbance of state ``i`` of model ``r`` with its 1-ci band: DataFrame (``mean``, ``lower``, ``upper``)
+        on the model's index, as ``get_state`` returns the state itself; ``ci=None`` returns the mean Series."""
+        from pandas import DataFrame
+
+        if i < 0 or i >= self.N + self.K:
+            raise IndexError("Value of i must be >=0 and <%d" % (self.N + self.K))
+        mean, variance = self.get_state_disturbances(alpha)
+        L = int(self.batch.lengths[r])
+        frame = lambda a: DataFrame(a[r, :L].cpu().numpy(), index=self.batch.index[r], columns=self._state_columns(r)).iloc[:, i]  # noqa: E731
+        return self._band(frame(mean), frame(variance) if ci is not None else None, ci)
+
+    def screen_breaks(self, alpha=None, t_first=1, min_information=1e-6):
+        """One row per (model, state): where the state equation failed most.  DataFrame indexed (model, state) -- states named
+        as ``get_state_means`` names them -- with ``max_abs_u`` (the largest auxiliary residual in magnitude over the steps
+        ``t >= t_first``), ``time`` (its time stamp), ``nobs`` (the number m of finite residuals searched) and ``pvalue``, the
+        Sidak-corrected two-sided normal p-value of the maximum of m residuals, ``1 - (1 - 2 Phi(-max|u|))^m``.  The correction
+        treats the m residuals as independent; neighbouring ones are positively correlated, so the p-value is on the
+        conservative side.  ``t_first=1`` leaves out the disturbance between the initial state and the first prediction.
+        Rows with m = 0 carry NaN (``time`` NaT)."""
+        from pandas import DataFrame, MultiIndex, NaT
+        from scipy.stats import norm
+
+        u = self.get_auxiliary_residuals(alpha, min_information).cpu().numpy()
+        rows, index = [], []
+        for r in range(self.R):
+            L = int(self.batch.lengths[r])
+            au = np.abs(u[r, int(t_first):L])
+            for i, name in enumerate(self._state_columns(r)):
+                index.append((r + self.shard[0], name))
+                m = int(np.isfinite(au[:, i]).sum())
+                if m == 0:
+                    rows.append((np.nan, NaT, 0, np.nan))
+                    continue
+                t = int(np.nanargmax(au[:, i]))
+                umax = float(au[t, i])
+                rows.append((umax, self.batch.index[r][t + int(t_first)], m, -np.expm1(m * np.log1p(-2.0 * norm.cdf(-umax)))))
+        return DataFrame(rows, columns=["max_abs_u", "time", "nobs", "pvalue"],
+                         index=MultiIndex.from_tuples(index, names=["model", "state"]))
 
     # ------------------------------------------------------------------ posterior draws (simulation smoother)
     def _draws(self, what, ndraws, seed, alpha, antithetic):

@@ -136,6 +136,11 @@ hipError_t dispatch_loo(int N, int K, const mk::AdjointArgs *na, const mk::Smoot
     const mk::ShapeOps *o = find_ops(N, K);
     return o ? o->loo(na, wa, s) : hipErrorInvalidValue;
 }
+hipError_t dispatch_disturb(int N, int K, const mk::AdjointArgs &a, hipStream_t s)
+{
+    const mk::ShapeOps *o = find_ops(N, K);
+    return o ? o->disturb(a, s) : hipErrorInvalidValue;
+}
 // workspace of the generic smoother: grown on demand, stream-ordered reuse (every launch of a context is on its stream)
 hipError_t generic_workspace(mk_context *ctx, long B, int n, double **ws)
 {
@@ -950,6 +955,30 @@ MK_API int mk_set_adjoint_updates(mk_context *ctx, double *d_buf, int64_t capaci
     return MK_OK;
 }
 
+// what every mode of the adjoint walks reads: the problem and the filtered records the recording forward pass left in d_work
+static mk::AdjointArgs adjoint_walk_args(const mk_problem *p, const double *d_work, int64_t record_stride, int time_major)
+{
+    mk::AdjointArgs a;
+    memset(&a, 0, sizeof(a));
+    a.B = p->n_instances;
+    a.R = p->n_records;
+    a.T = p->T;
+    a.bs = time_major ? 1 : p->T;
+    a.ts = time_major ? p->n_instances : 1;
+    a.rs = record_stride;
+    a.obs_bs = p->obs_time_major ? 1 : p->T;
+    a.obs_ts = p->obs_time_major ? p->n_records : 1;
+    a.obs = p->d_obs;
+    a.phi = p->d_phi;
+    a.q = p->d_q;
+    a.loadings = p->d_loadings;
+    a.obsvar = p->d_obsvar;
+    a.x0 = p->d_x0;
+    a.P0 = p->d_P0;
+    a.F = d_work;
+    return a;
+}
+
 MK_API int mk_loglik_grad(mk_context *ctx, const mk_problem *p, double *d_work, int time_major, double *d_mle,
                           int64_t *d_sigmacount, double *d_gphi, double *d_gq, uint32_t *d_status)
 {
@@ -996,27 +1025,10 @@ MK_API int mk_loglik_grad_phases(mk_context *ctx, const mk_problem *p, double *d
         if (rc) return rc;
     }
     if (!(phases & MK_GRAD_BACKWARD)) return MK_OK;
-    mk::AdjointArgs a;
-    memset(&a, 0, sizeof(a));
+    mk::AdjointArgs a = adjoint_walk_args(p, d_work, o.record_stride, time_major);
     a.upd = upd;
     a.us = upd ? us : 0;
-    a.B = p->n_instances;
-    a.R = p->n_records;
-    a.T = p->T;
     a.warmup = p->warmup;
-    a.bs = time_major ? 1 : p->T;
-    a.ts = time_major ? p->n_instances : 1;
-    a.rs = o.record_stride;
-    a.obs_bs = p->obs_time_major ? 1 : p->T;
-    a.obs_ts = p->obs_time_major ? p->n_records : 1;
-    a.obs = p->d_obs;
-    a.phi = p->d_phi;
-    a.q = p->d_q;
-    a.loadings = p->d_loadings;
-    a.obsvar = p->d_obsvar;
-    a.x0 = p->d_x0;
-    a.P0 = p->d_P0;
-    a.F = d_work;
     a.sigmacount = (const long long *)d_sigmacount;
     a.gphi = d_gphi;
     a.gq = d_gq;
@@ -1074,24 +1086,7 @@ MK_API int mk_loo(mk_context *ctx, const mk_problem *p, double *d_work, int time
         o.d_sigmas = d_work + n + n * n;
         o.d_detfs = o.d_sigmas + 1;
         if (int rc = do_filter(ctx, p, &o)) return rc;
-        mk::AdjointArgs a;
-        memset(&a, 0, sizeof(a));
-        a.B = p->n_instances;
-        a.R = p->n_records;
-        a.T = p->T;
-        a.bs = time_major ? 1 : p->T;
-        a.ts = time_major ? p->n_instances : 1;
-        a.rs = ws;
-        a.obs_bs = p->obs_time_major ? 1 : p->T;
-        a.obs_ts = p->obs_time_major ? p->n_records : 1;
-        a.obs = p->d_obs;
-        a.phi = p->d_phi;
-        a.q = p->d_q;
-        a.loadings = p->d_loadings;
-        a.obsvar = p->d_obsvar;
-        a.x0 = p->d_x0;
-        a.P0 = p->d_P0;
-        a.F = d_work;
+        mk::AdjointArgs a = adjoint_walk_args(p, d_work, ws, time_major);
         a.loo_means = d_loo_means;
         a.loo_vars = d_loo_vars;
         a.scale = p->d_scale;
@@ -1259,6 +1254,50 @@ MK_API int mk_draw_normals(mk_context *ctx, uint64_t seed, int64_t first_instanc
     a.raw = raw != 0;
     a.out = d_out;
     MK_HIP(mk::launch_draw_normals(a, ctx->stream));
+    return MK_OK;
+}
+
+// ---- smoothed state disturbances (the adjoint walks in their disturbance mode) ----
+MK_API int64_t mk_disturbance_work_stride(int64_t N, int64_t K)
+{
+    if (N < 1 || K < 1 || N + K > 64 || !specialised(N, K)) return 0;
+    return mk::record_stride((int)(N + K));
+}
+
+MK_API int mk_disturbances(mk_context *ctx, const mk_problem *p, double *d_work, int time_major, double *d_r, double *d_ninfo,
+                           uint32_t *d_status)
+{
+    MK_CTX(ctx);
+    if (int rc = check_problem(p)) return rc;
+    if (!d_work || !d_r || !d_ninfo) return fail(MK_ERR_INVALID, "mk_disturbances: d_work, d_r and d_ninfo are required");
+    if (!p->d_obs || !p->d_loadings) return fail(MK_ERR_INVALID, "d_obs and d_loadings are required");
+    const int64_t ws = mk_disturbance_work_stride(p->N, p->K);
+    if (!ws || ctx->variant[MK_VARIANT_KERNEL_FAMILY] == 1)
+        return fail(MK_ERR_SHAPE, "mk_disturbances serves specialised shapes with N + K <= 64 (ahead-of-time list or a shape module); "
+                                  "N=%lld, K=%lld is not one%s", (long long)p->N, (long long)p->K,
+                    ws ? " in this context (the size-generic kernel family is selected)" : "");
+    const int64_t n = p->N + p->K;
+    const draw_buffer bufs[3] = {{d_work, p->n_instances * p->T * ws, "d_work (n_instances * T * mk_disturbance_work_stride(N, K) doubles)"},
+                                 {d_r, p->n_instances * p->T * n, "d_r (n_instances * T * (N + K) doubles)"},
+                                 {d_ninfo, p->n_instances * p->T * n, "d_ninfo (n_instances * T * (N + K) doubles)"}};
+    if (int rc = draw_buffers_fit("mk_disturbances", bufs, 3)) return rc;
+    // the recording forward pass of mk_loglik_grad (filtered records; no update tape: the walk recomputes), then the walk
+    mk_outputs o;
+    memset(&o, 0, sizeof(o));
+    o.d_status = d_status;
+    o.d_F = d_work;
+    o.d_Pf = d_work + n;
+    o.d_sigmas = d_work + n + n * n;
+    o.d_detfs = o.d_sigmas + 1;
+    o.time_major = time_major;
+    o.record_stride = ws;
+    if (int rc = do_filter(ctx, p, &o)) return rc;
+    mk::AdjointArgs a = adjoint_walk_args(p, d_work, ws, time_major);
+    a.dist_r = d_r;
+    a.dist_n = d_ninfo;
+    MK_HIP(timing_start(ctx, 1));
+    MK_HIP(dispatch_disturb((int)p->N, (int)p->K, a, ctx->stream));
+    MK_HIP(timing_stop(ctx, 1)); // reported in the smoother slot of mk_last_kernel_ms / mk_kernel_ms_totals
     return MK_OK;
 }
 

@@ -106,11 +106,18 @@ struct AdjointArgs {
     double *gphi, *gq;               // [B,n] gradient of -2 log L w.r.t. diag(Phi), diag(Q)
     const double *upd;               // update tape written by the recording forward pass (FilterArgs.upd), or NULL: recompute
     long us;                         // its stride per (model, step), adjoint_update_stride_c(N, K)
-    // leave-one-out walk (adjoint_kernel<.., LOO = true>, ShapeOps::loo): [.,N] per (b,t), same (bs, ts) addressing as the records;
+    // leave-one-out walk (adjoint_kernel<.., AdjointMode::Loo>, ShapeOps::loo): [.,N] per (b,t), same (bs, ts) addressing as the records;
     // scale / offset [R,N] or NULL as in mk_problem.  Unused by the gradient.
     double *loo_means, *loo_vars;
     const double *scale, *offset;
+    // disturbance walk (AdjointMode::Dist, ShapeOps::disturb): r_t and diag(N_t) of Durbin & Koopman, [.,n] per (b,t), same (bs, ts)
+    // addressing as the records.  Unused by the gradient and by the leave-one-out walk.
+    double *dist_r, *dist_n;
 };
+
+// what a backward walk of adjoint_kernel / adjoint_wide_kernel is for: the parameter gradient, or -- with unit weights on every
+// step -- the leave-one-out pairs of the observed cells (n <= 16) or the state disturbances' r_t and diag(N_t)
+enum class AdjointMode { Grad, Loo, Dist };
 
 struct SparseArgs { // objective of ONE record (all instances share it), observed steps only
     long B, T, warmup;
@@ -133,6 +140,7 @@ struct SparseArgs { // objective of ONE record (all instances share it), observe
 // there for every MK_SHAPES entry; the run-time (N, K) is resolved to a compiled <N, K> once, by the lookup in shape_ops().
 template <int N, int K> hipError_t launch_split_nk(const FilterArgs &a, hipStream_t s);         // mk_split.hip: wide models, N series on the lanes + replicated factor block (hipErrorNotSupported: not served)
 template <int N, int K> hipError_t launch_adjoint_wide_nk(const AdjointArgs &a, hipStream_t s); // mk_split.hip: n > 16
+template <int N, int K> hipError_t launch_disturb_wide_nk(const AdjointArgs &a, hipStream_t s); // mk_split.hip: n > 16, AdjointMode::Dist
 template <int N, int K> hipError_t launch_smoother_wide_nk(const SmootherArgs &a, hipStream_t s); // mk_wide.hip (n > 16)
 template <int N, int K> hipError_t launch_wave_nk(const SmootherArgs &a, hipStream_t s);          // mk_wide.hip: the round-1 kernel
 template <int N, int K, int E, bool S> hipError_t launch_mfma_nk(const SmootherArgs &a, hipStream_t s); // mk_wide.hip: epilogue E, packed-symmetric S
@@ -149,6 +157,8 @@ struct ShapeOps {
     hipError_t (*adjoint)(const AdjointArgs &, hipStream_t);
     // leave-one-out predictions (mk_loo): n <= 16 the adjoint walk over filtered records (*narrow), 16 < n <= 63 the tape walk (*wide)
     hipError_t (*loo)(const AdjointArgs *narrow, const SmootherArgs *wide, hipStream_t);
+    // smoothed state disturbances (mk_disturbances): the adjoint walk of the shape in its disturbance mode, n <= 64
+    hipError_t (*disturb)(const AdjointArgs &, hipStream_t);
 };
 const ShapeOps *shape_ops(int *count); // mk_kernels.hip: one row per MK_SHAPES entry, in list order
 // what a shape module must have been built against: the argument structs and the table row (mkmod_abi)

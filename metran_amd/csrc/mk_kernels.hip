@@ -1783,17 +1783,26 @@ __global__ void __launch_bounds__(256) fill_gaps_kernel(SparseArgs a, int n)
 //   sums per update and the two matrix-vector products are fused DPP broadcast-FMAs.  One model per
 //   16-lane group (n <= 16); wider models keep the finite-difference path.
 //   Checked against central differences of the oracle and a numpy restatement (tests/adjoint_ref.py).
-// LOO = true: the same walk with unit weights on every step (warmup ignored) is a LEAVE-ONE-OUT pass (mk_loo).  There
+// MODE = AdjointMode::Loo: the same walk with unit weights on every step (warmup ignored) is a LEAVE-ONE-OUT pass (mk_loo).  There
 //   xb = -2 r and Pb = N - r r' (the Durbin-Koopman quantities just after the update), so de Jong's deletion result for the
 //   observed cell (t, j) reads off the update's own a and c:
 //       D = 1/f + (c + a^2/4)/f^2,   E[y_tj | all other cells] = y_tj - (v + a/2)/(f D),   Var[z_j x_t | ...] = 1/D - R_j
 //   Lane j keeps its series' pair and stores it once a step (NaN where the series is not observed); no gradient sums are formed.
 //   Restated in tests/loo_ref.py.
+// MODE = AdjointMode::Dist: the same unit-weight walk writes out what it carries (mk_disturbances).  Once the updates of step t
+//   are pulled back, and before the pull-back through Phi, r_t = -xb/2 and N_t = Pb + r_t r_t' are the Durbin-Koopman backward
+//   quantities of the state equation x_t = Phi x_{t-1} + eta_t (t = 0: between the initial state and the first prediction):
+//       E[eta_t,i | Y] = q_i r_t,i        Var[eta_t,i | Y] = q_i - q_i^2 N_t,ii        u_t,i = r_t,i / sqrt(N_t,ii)
+//   (u: the auxiliary residual of Harvey & Koopman 1992, formed by the caller from the RAW pair -- never from a difference).
+//   Lane i < n stores r_t,i and N_t,ii = Pb[i][i] + r_t,i^2 (the gradient's diagonal select; a negative value from rounding is
+//   stored as 0, NaN stays NaN) at every step, observed or not; no gradient sums are formed and sigmacount is not read.
+//   Restated in tests/disturbance_ref.py.
 // =====================================================================================
-template <int N, int K, int G, bool LOO = false>
+template <int N, int K, int G, AdjointMode MODE = AdjointMode::Grad>
 __global__ void __launch_bounds__(256) adjoint_kernel(AdjointArgs a)
 {
     constexpr int n = N + K;
+    constexpr bool LOO = MODE == AdjointMode::Loo, DIST = MODE == AdjointMode::Dist, UNIT = LOO || DIST; // UNIT: weight 1 on every step
     static_assert(G == 16 && n <= 16, "adjoint kernel: one model per 16-lane group");
     using Gp = Group<G>;
     constexpr int GPB = 256 / G;
@@ -1835,7 +1844,7 @@ __global__ void __launch_bounds__(256) adjoint_kernel(AdjointArgs a)
     double ones[n];
 #pragma unroll
     for (int c = 0; c < n; ++c) ones[c] = 1.0;
-    const long sctot = LOO ? 0 : a.sigmacount[inst]; // observed steps in total (written by the forward filter)
+    const long sctot = UNIT ? 0 : a.sigmacount[inst]; // observed steps in total (written by the forward filter)
     long rem = 0;                          // observed steps already walked (from the end)
     const double one = 1.0;
 
@@ -1877,6 +1886,18 @@ __global__ void __launch_bounds__(256) adjoint_kernel(AdjointArgs a)
         lo.scale = a.scale ? a.scale[rec * N + jr] : 1.0;
         lo.offset = a.offset ? a.offset[rec * N + jr] : 0.0;
     }
+    // Dist: lane i < n's two output cells of the step walked
+    struct DistLane {
+        double *orr, *on;
+        long step;
+    };
+    [[maybe_unused]] typename std::conditional<DIST, DistLane, NoLoo>::type di;
+    if constexpr (DIST) {
+        const bool own = live && lane < n;
+        di.orr = own ? a.dist_r + (inst * a.bs + (T - 1) * a.ts) * n + lane : nullptr;
+        di.on = own ? a.dist_n + (inst * a.bs + (T - 1) * a.ts) * n + lane : nullptr;
+        di.step = a.ts * n;
+    }
     load_prev(T - 1, xnext, Pnext);
     ynext = obase[(T - 1) * ostep];
 
@@ -1894,7 +1915,7 @@ __global__ void __launch_bounds__(256) adjoint_kernel(AdjointArgs a)
 
         if constexpr (LOO) lo.mean = lo.var = __builtin_nan("");
         if (vm != 0) { // uniform within the lane group
-            const double w = LOO ? 1.0 : ((sctot - rem - 1 >= a.warmup) ? 1.0 : 0.0); // compressed index of this step (:563-564)
+            const double w = UNIT ? 1.0 : ((sctot - rem - 1 >= a.warmup) ? 1.0 : 0.0); // compressed index of this step (:563-564)
             ++rem;
             // ---- forward: prediction and scalar updates of step t, as filter_kernel ----
             double x = phi_r * xprev, P[n];
@@ -2008,6 +2029,25 @@ __global__ void __launch_bounds__(256) adjoint_kernel(AdjointArgs a)
             xb *= phi_r;
             continue;
         }
+        if constexpr (DIST) { // r_t and N_t,ii as they stand between the updates of step t and the pull-back through Phi
+            double diag = 0.0;
+            sfor<0, n>(MK_LAMBDA(cc) {
+                constexpr int c = decltype(cc)::value;
+                diag = (c == r) ? Pb[c] : diag;
+            });
+            if (di.orr) {
+                const double rr = -0.5 * xb;
+                const double nn = fma(rr, rr, diag);
+                *di.orr = rr;
+                *di.on = nn < 0.0 ? 0.0 : nn; // NaN stays NaN
+                di.orr -= di.step;
+                di.on -= di.step;
+            }
+#pragma unroll
+            for (int c = 0; c < n; ++c) Pb[c] *= pp[c];
+            xb *= phi_r;
+            continue;
+        }
         // ---- prediction adjoint ----
         double diag = 0.0, ts0 = 0.0, ts1 = 0.0;
         double phv = phi_r;
@@ -2024,7 +2064,7 @@ __global__ void __launch_bounds__(256) adjoint_kernel(AdjointArgs a)
         gphi = fma(xb, xprev, fma(2.0, ts0 + ts1, gphi));
         xb *= phi_r;
     }
-    if (!LOO && live && lane < n) {
+    if (!UNIT && live && lane < n) {
         if (a.gphi) a.gphi[inst * n + lane] = gphi;
         if (a.gq) a.gq[inst * n + lane] = gq;
     }
@@ -2289,11 +2329,26 @@ static hipError_t launch_loo_nk(const AdjointArgs *na, const SmootherArgs *wa, h
     if constexpr (n <= 16) {
         if (!na || !na->loo_means || !na->loo_vars) return hipErrorInvalidValue;
         constexpr int GPB = 256 / 16;
-        hipLaunchKernelGGL((adjoint_kernel<N, K, 16, true>), dim3((unsigned)((na->B + GPB - 1) / GPB)), dim3(256), 0, s, *na);
+        hipLaunchKernelGGL((adjoint_kernel<N, K, 16, AdjointMode::Loo>), dim3((unsigned)((na->B + GPB - 1) / GPB)), dim3(256), 0, s, *na);
         return hipGetLastError();
     } else {
         if (!wa) return hipErrorInvalidValue;
         return launch_loo_dk_nk<N, K>(*wa, s);
+    }
+}
+
+// smoothed state disturbances: the adjoint walk of the shape in its disturbance mode (n <= 16 here, wider in mk_split.hip)
+template <int N, int K>
+static hipError_t launch_disturb_nk(const AdjointArgs &a, hipStream_t s)
+{
+    constexpr int n = N + K;
+    if constexpr (n <= 16) {
+        if (!a.dist_r || !a.dist_n) return hipErrorInvalidValue;
+        constexpr int GPB = 256 / 16;
+        hipLaunchKernelGGL((adjoint_kernel<N, K, 16, AdjointMode::Dist>), dim3((unsigned)((a.B + GPB - 1) / GPB)), dim3(256), 0, s, a);
+        return hipGetLastError();
+    } else {
+        return launch_disturb_wide_nk<N, K>(a, s);
     }
 }
 
@@ -2302,7 +2357,8 @@ static hipError_t launch_loo_nk(const AdjointArgs *na, const SmootherArgs *wa, h
 const ShapeOps *shape_ops(int *count)
 {
 #define MK_SHAPE_ROW(NN, KK) \
-    {NN, KK, launch_filter_nk<NN, KK>, launch_smoother_nk<NN, KK>, launch_sparse_nk<NN, KK>, launch_adjoint_nk<NN, KK>, launch_loo_nk<NN, KK>},
+    {NN, KK, launch_filter_nk<NN, KK>, launch_smoother_nk<NN, KK>, launch_sparse_nk<NN, KK>, launch_adjoint_nk<NN, KK>, launch_loo_nk<NN, KK>, \
+     launch_disturb_nk<NN, KK>},
     static const ShapeOps ops[] = {MK_SHAPES(MK_SHAPE_ROW)};
 #undef MK_SHAPE_ROW
     *count = (int)(sizeof(ops) / sizeof(ops[0]));

@@ -1321,9 +1321,15 @@ typedef __attribute__((address_space(3))) void adj_lds_void_t;
 typedef __attribute__((address_space(3))) char adj_lds_char_t;
 typedef __attribute__((address_space(1))) const void adj_global_cvoid_t;
 
-template <int N, int K, bool UPD>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) adjoint_wide_kernel(AdjointArgs a)
+// DIST (mk_disturbances; AdjointMode::Dist of adjoint_kernel, formulas there): the recompute form with unit weight on every step.
+// Lane i < n stores r_t,i = -xb/2 and N_t,ii = Pb[i][i] + r_t,i^2 once the updates of step t are pulled back, then (xb, Pb) go
+// back through Phi; the gradient sums are not formed, so the filtered row of step t-1 is not kept in LDS, and sigmacount is not read.
+template <int N, int K, bool UPD, bool DIST = false>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DIST && N + K > 36 ? 1 : 2, 2))) adjoint_wide_kernel(AdjointArgs a)
 {
+    // (DIST keeps no filtered row in LDS, so beyond n = 36 -- where two wavefronts' rows of P and Pb no longer fit 256 registers --
+    // LDS would still admit two wavefronts per SIMD and the compiler would spill to hold them: it is told that one will do)
+    static_assert(!(DIST && UPD), "the disturbance walk recomputes the updates");
     constexpr int n = N + K;
     static_assert(n > 16 && n <= 64, "one model per wavefront, 16 < n <= 64");
     using Gp = Group<64>;
@@ -1343,13 +1349,16 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     const double lmask = lane < n ? 1.0 : 0.0;
     const long T = a.T;
 
-    __shared__ __attribute__((aligned(16))) double lds[DSB + NP + GT + n * NP + NP];
+    constexpr int PLN = DIST ? 0 : n * NP;      // the filtered covariance of step t-1 is the gradient's
+    constexpr int LN = DIST ? 2 * 64 : 0;       // DIST: the lanes' q and R wait in LDS too (registers: no scratch at (32,4))
+    __shared__ __attribute__((aligned(16))) double lds[DSB + NP + GT + PLN + NP + LN];
     double *dS = lds;                           // per-update table of the current step (first: its LDS address is the array's own)
     [[maybe_unused]] adj_lds_char_t *const dS3 = (adj_lds_char_t *)lds;
     double *phim = dS + DSB;                    // diag(Phi)
     double *gtab = phim + NP;                   // loadings [N][K]
     double *PL = gtab + GT;                     // filtered covariance of step t-1, row r at PL + r NP
-    double *dbv = PL + n * NP;                  // db of the current update
+    double *dbv = PL + PLN;                     // db of the current update
+    [[maybe_unused]] double *qlane = dbv + NP + lane, *rlane = qlane + 64; // DIST: this lane's q_r and R_jr
 
     const double phi_r = a.phi[inst * n + r];
     const double q_r = a.q[inst * n + r];
@@ -1361,8 +1370,15 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     phim[r] = phi_r;
 #pragma unroll
     for (int k = 0; k < K; ++k) gtab[jr * K + k] = gam[k];
+    if constexpr (DIST) {
+        *qlane = q_r;
+        *rlane = rvar;
+    }
     wave_lds_sync();
-    const long sctot = a.sigmacount[inst];      // observed steps in total (written by the forward filter)
+    // the lane's own loadings, q and R at their point of use: registers held across the walk, or (DIST) read back from LDS
+    const double *gown = gtab + jr * K;
+    auto gam_at = [&](auto k) __attribute__((always_inline)) { return DIST ? gown[decltype(k)::value] : gam[decltype(k)::value]; };
+    const long sctot = DIST ? 0 : a.sigmacount[inst]; // observed steps in total (written by the forward filter)
     long rem = 0;                               // observed steps already walked (from the end)
 
     const long RS = a.rs;
@@ -1435,10 +1451,10 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
         const double y = obase[t * ostep];
         if constexpr (UPD) __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0): this step's block of the update tape has landed in LDS
         wave_lds_sync(); // the previous step's reads of PL are complete
-        store_row<n>(PL + r * NP, P);
+        if constexpr (!DIST) store_row<n>(PL + r * NP, P);
         const unsigned long long vm = __ballot(lane < N && isfinite(y));
         if (vm != 0) {
-            const double w = (sctot - rem - 1 >= a.warmup) ? 1.0 : 0.0; // compressed index of this step (:563-564)
+            const double w = DIST ? 1.0 : ((sctot - rem - 1 >= a.warmup) ? 1.0 : 0.0); // compressed index of this step (:563-564)
             ++rem;
             int cnt = 0;
             if constexpr (UPD) {
@@ -1448,7 +1464,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
             double x = phi_r * xprev;
             {
                 int rv = r;
-                double qv = q_r;
+                double qv = DIST ? *qlane : q_r;
                 asm volatile("" : "+v"(rv), "+v"(qv));
                 sweep(phim, [&](auto cc, double ph) __attribute__((always_inline)) {
                     constexpr int c = decltype(cc)::value;
@@ -1458,7 +1474,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
             for (unsigned long long m = vm; m; m &= m - 1) {
                 const int j = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(m));
                 double vl = y - x;
-                sfor<0, K>(MK_LAMBDA(k) { vl = fma(-gam[decltype(k)::value], Gp::template bcast<N + decltype(k)::value>(x), vl); });
+                sfor<0, K>(MK_LAMBDA(k) { vl = fma(-gam_at(k), Gp::template bcast<N + decltype(k)::value>(x), vl); });
                 const double v = readlane_f64(vl, j);
                 double dr = 0.0;
                 pick_column_all<N, n>(dr, j, P);
@@ -1466,8 +1482,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
                 sfor<0, K>(MK_LAMBDA(k) { dr = fma(P[N + decltype(k)::value], gp[decltype(k)::value], dr); });
                 double *drow = dS + cnt * DS;
                 drow[r] = dr;
-                double fl = rvar + dr;
-                sfor<0, K>(MK_LAMBDA(k) { fl = fma(Gp::template bcast<N + decltype(k)::value>(dr), gam[decltype(k)::value], fl); });
+                double fl = (DIST ? *rlane : rvar) + dr;
+                sfor<0, K>(MK_LAMBDA(k) { fl = fma(Gp::template bcast<N + decltype(k)::value>(dr), gam_at(k), fl); });
                 const double f = readlane_f64(fl, j);
                 const double rf = rcp_nr(f);
                 const double kr = dr * rf;
@@ -1531,6 +1547,25 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
         }
         // next record into the (now dead) P row: in flight during the prediction adjoint; this loop stores nothing
         if (t > 0) load_prev(t - 1);
+        if constexpr (DIST) { // r_t and N_t,ii between the updates of step t and the pull-back through Phi
+            double diag = 0.0;
+            int rv = r;
+            asm volatile("" : "+v"(rv));
+            sweep(phim, [&](auto cc, double ph) __attribute__((always_inline)) {
+                constexpr int c = decltype(cc)::value;
+                diag = (c == rv) ? Pb[c] : diag;
+                Pb[c] = Pb[c] * ph * phi_r;
+            });
+            if (live && lane < n) {
+                const long o = (inst * a.bs + t * a.ts) * n + lane;
+                const double rr = -0.5 * xb;
+                const double nn = fma(rr, rr, diag);
+                a.dist_r[o] = rr;
+                a.dist_n[o] = nn < 0.0 ? 0.0 : nn; // NaN stays NaN
+            }
+            xb *= phi_r;
+            continue;
+        }
         // ---- prediction adjoint (Pprev from LDS) ----
         {
             double diag = 0.0, ts0 = 0.0, ts1 = 0.0;
@@ -1603,9 +1638,23 @@ hipError_t launch_adjoint_wide_nk(const AdjointArgs &a, hipStream_t s)
     }
 }
 
-#define MK_INSTANTIATE(NN, KK)                                                      \
-    template hipError_t launch_split_nk<NN, KK>(const FilterArgs &, hipStream_t); \
-    template hipError_t launch_adjoint_wide_nk<NN, KK>(const AdjointArgs &, hipStream_t);
+// the disturbance walk (mk_disturbances): the recompute form, whatever update tape the context holds
+template <int N, int K>
+hipError_t launch_disturb_wide_nk(const AdjointArgs &a, hipStream_t s)
+{
+    if constexpr (N + K > 16) {
+        if (!a.dist_r || !a.dist_n) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((adjoint_wide_kernel<N, K, false, true>), dim3((unsigned)a.B), dim3(64), 0, s, a);
+        return hipGetLastError();
+    } else {
+        return hipErrorNotSupported;
+    }
+}
+
+#define MK_INSTANTIATE(NN, KK)                                                               \
+    template hipError_t launch_split_nk<NN, KK>(const FilterArgs &, hipStream_t);          \
+    template hipError_t launch_adjoint_wide_nk<NN, KK>(const AdjointArgs &, hipStream_t); \
+    template hipError_t launch_disturb_wide_nk<NN, KK>(const AdjointArgs &, hipStream_t);
 MK_SHAPES(MK_INSTANTIATE)
 #undef MK_INSTANTIATE
 

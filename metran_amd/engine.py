@@ -746,6 +746,48 @@ class BatchedKalman:
                              self._p(res["loo_means"]), self._p(res["loo_vars"]), self._p(res["status"])))
         return res
 
+    # ------------------------------------------------------------------ smoothed state disturbances
+    def disturbances_supported(self):
+        """True when ``disturbances`` serves this engine's shape (C ABI ``mk_disturbance_work_stride`` > 0): specialised
+        kernels and N + K <= 64 -- ``adjoint_kernel`` for N + K <= 16, ``adjoint_wide_kernel`` above, in their disturbance mode."""
+        return (self.loadings is not None and self.get_variant("kernel_family") == "specialised"
+                and int(self._L.mk_disturbance_work_stride(self.N, self.K)) > 0)
+
+    def _disturbance_stride(self):
+        if not self.disturbances_supported():
+            raise MetranHipError("state disturbances serve specialised shapes with N + K <= 64; (N=%s, K=%s) is not one"
+                                 % (self.N, getattr(self, "K", None)))
+        return int(self._L.mk_disturbance_work_stride(self.N, self.K))
+
+    def alloc_disturbances(self, B):
+        """Buffers of ``disturbances`` for B instances (the forward pass's workspace + the two outputs), for callers that run
+        it repeatedly (pass them back as ``buffers=``)."""
+        torch = _torch()
+        return {"_work": self._empty_bt(B, self.T, self._disturbance_stride()),
+                "r": self._empty_bt(B, self.T, self.n), "ninfo": self._empty_bt(B, self.T, self.n),
+                "status": torch.zeros(B, dtype=torch.int32, device=self.device)}
+
+    def disturbances(self, phi, q, x0=None, P0=None, buffers=None):
+        """Smoothed STATE DISTURBANCES for B instances (C ABI ``mk_disturbances``): the Durbin-Koopman backward pair of the
+        state equation x_t = phi o x_{t-1} + eta_t, ``r[b,t,i]`` and ``ninfo[b,t,i]`` = N_t,ii, for every state of every step
+        (t = 0: between the initial state and the first prediction), from which
+        ``E[eta | Y] = q r``, ``Var[eta | Y] = q - q^2 ninfo`` and the auxiliary residual ``u = r / sqrt(ninfo)`` (Harvey &
+        Koopman 1992; unit spread under the model, large where the state equation failed).  The raw pair is returned so that
+        ``u`` is never formed from a difference.  Two launches: the recording forward pass and one backward walk.
+        Returns a dict with ``r, ninfo`` ``[B,T,n]`` and ``status`` (the filter's MK_FLAG_* bits)."""
+        stride = self._disturbance_stride()
+        prob, keep, B = self._problem(phi, q, 0, x0, P0)
+        res = buffers if buffers is not None else self.alloc_disturbances(B)
+        for key, tail in (("_work", stride), ("r", self.n), ("ninfo", self.n)):
+            t = res[key]
+            if tuple(t.shape) != (B, self.T, tail) or self._layout(t) is not t:
+                raise ValueError("buffers[%r] must be a [%d,%d,%d] tensor in the engine's layout (alloc_disturbances)"
+                                 % (key, B, self.T, tail))
+        self._bind_stream()
+        check(self._L.mk_disturbances(self._ctx, ctypes.byref(prob), self._p(res["_work"]), 1 if self.time_major else 0,
+                                      self._p(res["r"]), self._p(res["ninfo"]), self._p(res["status"])))
+        return res
+
     # ------------------------------------------------------------------ one-step-ahead innovations
     _INNOVATION_OUTPUTS = ("v", "f", "pred_mean", "pred_var")
 
