@@ -46,11 +46,46 @@ struct RecordIO;
 #ifndef MK_FILTER_LDS_STORES
 #define MK_FILTER_LDS_STORES 1
 #endif
+// Deferred record emission of the 16-lane record filter (MK_FILTER_DEFER=0 builds the form that emits both records in one
+// block at the end of the step, for A/B runs).  With one wavefront per SIMD nothing else can issue while a wavefront waits,
+// and the end-of-step block was one wait after another: the per-step logarithm's dependent chain, the image's write -> read
+// round trip through LDS, then eight stores behind the reads' lgkmcnt waits -- from all four wavefronts of a CU at once.
+// The deferred schedule spreads the same instructions over the scalar updates (SLOT j = the point behind update j):
+//   predicted record : into imgP right after the prediction (as before);
+//   filtered record  : into imgF at the end of step t (as before); it leaves during step t + 1, the record of the last
+//                      step after the loop;
+//   chunks           : the step's chunks (predicted and filtered alternating) are gathered ONE per slot from slot 0 on and
+//                      stored one slot behind their gather, so a store never waits for its LDS read, at most three chunks
+//                      are held in registers, and the CU's vector-memory path sees one store per wavefront and update
+//                      instead of a burst of eight;
+//   logarithm        : sigma, the normalised product of the innovation variances and its exponent are CARRIED into step
+//                      t + 1 (they stay in the registers they are in: nothing else is live there before update 0), where
+//                      detf, the pad and the running sums are formed between the prediction and update 0 -- no store and
+//                      no LDS read waits behind that chain any more.  (Cutting the chain into pieces behind updates 0..2
+//                      held its state across the updates and spilled; the f64 pipe is issue-bound, so the chain costs its
+//                      issue slots wherever it stands.)
+// Every multiply-add, its operands and its order are those of the undeferred form: the outputs are bit-identical.
+#ifndef MK_FILTER_DEFER
+#define MK_FILTER_DEFER 1
+#endif
+#ifndef MK_FILTER_DEFER_LOG
+#define MK_FILTER_DEFER_LOG 1
+#endif
+// ... the record kernels the schedule applies to are held to two resident wavefronts per SIMD (256 VGPRs; the 8192-model
+// flights run two), which they kept without being asked before -- up to 10 states and 16 hoisted loadings, where that holds
+// without scratch (compile-checked: (7,3) spills 40 bytes under it and is left to the allocator)
+#define MK_FILTER_WAVES(n, NK, G, OUT) ((MK_FILTER_DEFER && MK_FILTER_LDS_STORES && (G) == 16 && ((OUT) == 1 || (OUT) == 3) && (n) <= 10 && (NK) <= 16) ? 2 : 1)
+// chunk q of a step's emission sequence is gathered at slot min(q, N - 1) and stored one slot later; slot N is the end of
+// the step, behind the put of the filtered image
+template <int N>
+constexpr int filter_gather_slot(int q) { return q < N - 1 ? q : N - 1; }
+template <int N>
+constexpr int filter_store_slot(int q) { return filter_gather_slot<N>(q) + 1; }
 
 // (two resident wavefronts per SIMD are asked for only while the wide variant's two n-double row arrays fit
 // 256 VGPRs: compile-checked at n = 64, the constraint spilled 1.1 KB per lane)
 template <int N, int K, int G, int OUT, bool BOOK, bool SYM>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 64 && N + K <= 40 ? MK_WIDE_FILTER_WAVES : 1))) filter_kernel(FilterArgs a)
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 64 && N + K <= 40 ? MK_WIDE_FILTER_WAVES : MK_FILTER_WAVES(N + K, N * K, G, OUT)))) filter_kernel(FilterArgs a)
 {
     static_assert(!SYM || OUT == 1 || OUT == 3, "packed-symmetric layout applies to record outputs");
     constexpr int n = N + K;
@@ -162,8 +197,77 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 6
         RIO::clear_tail(imgP, lane64);
         RIO::clear_tail(imgF, lane64);
         RIO::put_pad(imgP, gw, 0.0, 0.0);
+        if constexpr (MK_FILTER_DEFER) {
+            RIO::put(imgF, gw, r, x, P); // what step 0 finds in the carried record's image
+            RIO::put_pad(imgF, gw, 0.0, 0.0);
+        }
     }
     double pad0 = 0.0, pad1 = 0.0;
+    double sum_sig = 0.0, sum_det = 0.0;
+    long sc = 0; // compressed index of the next observed step
+    // ---- deferred emission (MK_FILTER_DEFER, see the top of the file) ----
+    constexpr bool FDEFER = MK_FILTER_DEFER && LDSOUT;
+    // the packed-symmetric two-record kernel holds eight more map registers: with the carried logarithm it spills at n = 10,
+    // so there detf is formed at the end of its own step as before (and the step's last chunk store is issued before it)
+    constexpr bool FDLOG = FDEFER && BOOK && MK_FILTER_DEFER_LOG && !(SYM && OUT == 1);
+    constexpr int FPER = RIO::PER;
+    constexpr int FNC = (OUT == 1 ? 2 : 1) * FPER; // chunks a lane moves per step; OUT == 1: P0 F0 P1 F1 ...
+    double c_sigma = 0.0, c_fmant = 1.0; // sigma and the normalised product of the f's of the carried step
+    int c_fexp = 0;                      // ... and the product's exponent
+    bool c_has = false;                  // it observed something (then its compressed index is sc - 1)
+    typename RIO::chunk_t ch[FNC];
+    // where the carried filtered record goes.  Step 0 has none: it stores the initial moments (put below) to record 0, where
+    // the same lanes store the filtered record of step 0 one step later -- a branch around the stores of step 0 costs 14
+    // VGPRs in every step (the chunks then live across control flow), which the kernel does not have
+    double *recFc = a.F;
+    auto carried_book = [&](long tc) __attribute__((always_inline)) { // the bookkeeping of the carried step tc, as in the undeferred form
+        if (c_has) {
+            const long csc = sc - 1;
+            int le;
+            const double lm = log_mant(c_fmant, le);
+            const double detf = fma((double)(c_fexp + le), kLn2, lm);
+            if (csc == tc) {
+                pad0 = c_sigma;
+                pad1 = detf;
+            } else if (lead && a.sigmas) {
+                // record csc is older than the carried step's: its chunk stores (with a zero pad) were issued at least one
+                // step ago, this store follows them in program order
+                *reinterpret_cast<v2d *>(a.F + (inst * a.bs + csc * a.ts) * RS + NVO) = v2d{c_sigma, detf};
+            }
+            if (csc >= a.warmup) {
+                sum_det += detf;
+                sum_sig += c_sigma;
+            }
+        }
+        RIO::put_pad(imgF, gw, pad0, pad1); // before the gathers of the carried record
+        pad0 = pad1 = 0.0;
+    };
+    auto chunk_store = [&](auto qc) __attribute__((always_inline)) {
+        constexpr int q = decltype(qc)::value, m = OUT == 1 ? q / 2 : q;
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (OUT == 1 && q % 2 == 0) {
+            RIO::store_one(recP, rmap, m, ch[q]);
+        } else {
+            RIO::store_one(recFc, rmap, m, ch[q]);
+        }
+    };
+    auto slot = MK_LAMBDA(jc) { // behind update j (fixed series indices: also where the update itself is masked out)
+        if constexpr (FDEFER) {
+            constexpr int j = decltype(jc)::value;
+            sfor<0, FNC>(MK_LAMBDA(qc) { // the chunks gathered at the slot before
+                if constexpr (filter_store_slot<N>(decltype(qc)::value) == j) chunk_store(qc);
+            });
+            sfor<0, FNC>(MK_LAMBDA(qc) {
+                constexpr int q = decltype(qc)::value, m = OUT == 1 ? q / 2 : q;
+                if constexpr (filter_gather_slot<N>(q) == j) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    wave_lds_sync(); // the image's puts (this step's imgP, last step's imgF and its pad) are visible
+                    ch[q] = RIO::gather((OUT == 1 && q % 2 == 0) ? imgP : imgF, rmap, m); // (step 0: the initial moments)
+                }
+            });
+            __builtin_amdgcn_sched_barrier(0); // the stores stay one update apart
+        }
+    };
     // TAPE: block of (model, step) = N (state tape: N + K) entries [ vector in the observable basis (n) | s0 s1 s2 0 ] of
     // XS = n + 4 doubles (mk_internal.h); lane r < n holds element r of an entry's vector
     [[maybe_unused]] constexpr int XS = tape_xs_c(N, K);
@@ -223,10 +327,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 6
     obs_issue(0);
     double ynext = 0.0;
 
-    double sum_sig = 0.0, sum_det = 0.0;
     double run_mant = 1.0; // !BOOK: prod of f over the counted steps, normalised
     long run_exp = 0;
-    long nobs = 0, sc = 0;
+    long nobs = 0;
     double fmin_seen = 1.0;
 
     for (long t0 = 0; t0 < T; t0 += TS) {
@@ -279,6 +382,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 6
             oP.advance(1);
         }
 
+        if constexpr (FDLOG) carried_book(t - 1); // detf, the pad and the sums of step t - 1 (nothing in step 0)
         // ---- sequential scalar updates (:341-378), observations in ascending series order ----
         double sigma = 0.0, fmant = 1.0;
         int fexp = 0;
@@ -443,7 +547,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 6
             fexp += __builtin_amdgcn_frexp_exp(fmant);
             fmant = __builtin_amdgcn_frexp_mant(fmant);
         } else if (ball == Gp::full_mask(N)) { // every model of this wavefront observes all N series: no masking
-            sfor<0, N>(update);
+            sfor<0, N>(MK_LAMBDA(jc) {
+                update(jc);
+                slot(jc);
+            });
         } else {
             sfor<0, N>(MK_LAMBDA(jc) {
                 if ((vm >> decltype(jc)::value) & 1) { // uniform within the model's lane group
@@ -452,16 +559,28 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 6
                     fexp += __builtin_amdgcn_frexp_exp(fmant); // keep the product normalised
                     fmant = __builtin_amdgcn_frexp_mant(fmant);
                 }
+                slot(jc); // outside the conditional: the gathers and stores of every step stand at the same series indices
             });
         }
 
         const int cnt = __popcll((unsigned long long)vm);
         double pad = 0.0; // records: what this lane writes into its pad slot of the filtered record
-        if (cnt > 0) { // :380-382 compressed bookkeeping
+        // undeferred logarithm: the scattered pad store below may go to the record of step t - 1, whose last chunk store
+        // (slot N) must precede it in program order
+        if constexpr (FDEFER && !FDLOG) slot(std::integral_constant<int, N>{});
+        if constexpr (FDLOG) {
+            // deferred: the logarithm, the pad and the running sums of this step are formed at the head of the next one
+            // (carried_book), with this step's own sc
+            c_has = cnt > 0;
+            c_sigma = sigma;
+            c_fmant = fmant;
+            c_fexp = fexp;
+            if (cnt > 0) ++sc;
+        } else if (cnt > 0) { // :380-382 compressed bookkeeping
             if constexpr (BOOK) {
-                int le;
-                const double lm = log_mant(fmant, le);
-                const double detf = fma((double)(fexp + le), kLn2, lm);
+                int le = 0;
+                const double lm = MK_TUNE_SKIP(a, 4) ? 0.5 : log_mant(fmant, le); // (timing build: a constant in the pad)
+                const double detf = MK_TUNE_SKIP(a, 4) ? lm : fma((double)(fexp + le), kLn2, lm);
                 if constexpr (RECF) {
                     // compressed entry sc lives in the pad of filtered record sc; sc == t unless an earlier
                     // step of this model was empty (then: one scattered 16-byte store, rare)
@@ -549,11 +668,50 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 6
             trec += tstep;
         }
 
-        if constexpr (LDSOUT) {
+        if constexpr (FDEFER) {
+            RIO::put(imgF, gw, r, x, P); // leaves in the next step (the last one: after the loop)
+            if constexpr (!FDLOG) {
+                RIO::put_pad(imgF, gw, pad0, pad1);
+                pad0 = pad1 = 0.0;
+            }
+            if constexpr (FDLOG) slot(std::integral_constant<int, N>{}); // the last chunk(s), gathered behind the last update
+            if constexpr (OUT == 1) recP += rstep;
+            recFc = recF;
+            recF += rstep;
+        } else if constexpr (LDSOUT) {
             RIO::put(imgF, gw, r, x, P);
             RIO::put_pad(imgF, gw, pad0, pad1);
             pad0 = pad1 = 0.0;
-            if constexpr (OUT == 1) {
+            if constexpr (MK_TUNE_SKIP(a, 1) || MK_TUNE_SKIP(a, 2)) {
+                // timing builds of the undeferred form (results meaningless): 1 = the LDS writes and reads without the global
+                // stores, 2 = the stores fed from registers (this lane's row) without the LDS round trip
+                typename RIO::chunk_t tP[FPER], tF[FPER];
+                if constexpr (MK_TUNE_SKIP(a, 2)) {
+#pragma unroll
+                    for (int m = 0; m < FPER; ++m) tP[m] = tF[m] = typename RIO::chunk_t{P[(2 * m) % n], P[(2 * m + 1) % n]};
+                } else {
+                    wave_lds_sync();
+#pragma unroll
+                    for (int m = 0; m < FPER; ++m) {
+                        if constexpr (OUT == 1) tP[m] = RIO::gather(imgP, rmap, m);
+                        tF[m] = RIO::gather(imgF, rmap, m);
+                    }
+                }
+#pragma unroll
+                for (int m = 0; m < FPER; ++m) {
+                    if constexpr (MK_TUNE_SKIP(a, 1)) {
+                        if constexpr (OUT == 1) asm volatile("" ::"v"(tP[m]));
+                        asm volatile("" ::"v"(tF[m]));
+                    } else {
+                        if constexpr (OUT == 1) RIO::store_one(recP, rmap, m, tP[m]);
+                    }
+                }
+                if constexpr (!MK_TUNE_SKIP(a, 1)) {
+#pragma unroll
+                    for (int m = 0; m < FPER; ++m) RIO::store_one(recF, rmap, m, tF[m]);
+                }
+                if constexpr (OUT == 1) recP += rstep;
+            } else if constexpr (OUT == 1) {
                 RIO::emit2(imgP, recP, imgF, recF, rmap);
                 recP += rstep;
             } else {
@@ -575,6 +733,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 6
     }
     }
 
+    if constexpr (FDEFER) {
+        if (T > 0) { // the last step's bookkeeping and its filtered record
+            if constexpr (FDLOG) carried_book(T - 1);
+            RIO::emit(imgF, recFc, rmap);
+        }
+    }
     // zero tail of the compressed arrays (np.zeros init, :307-308); record pads were written as zeros
     if (BOOK && !RECF) {
         for (long i = sc + lane; i < T; i += G) {
@@ -749,6 +913,11 @@ struct RecordIO {
     {
 #pragma unroll
         for (int m = 0; m < PER; ++m) rec_store(reinterpret_cast<chunk_t *>(base + mp.off[m]), tmp[m]);
+    }
+    // one chunk, for callers that place every store themselves (the filter's deferred schedule)
+    static __device__ __forceinline__ void store_one(double *base, const Map &mp, int m, chunk_t v)
+    {
+        rec_store(reinterpret_cast<chunk_t *>(base + mp.off[m]), v);
     }
     static __device__ __forceinline__ void emit2(const double *img0, double *base0, const double *img1, double *base1,
                                                  const Map &mp)

@@ -271,7 +271,9 @@ def prune():
 # machine so that the GPU box spends its minutes on kernels, not on hipcc
 TEST_SHAPES = [(7, 2), (11, 3), (14, 2), (20, 2), (16, 2), (32, 1), (48, 3), (17, 1), (17, 3), (20, 4), (11, 6), (12, 3), (9, 2), (19, 2),
                # tests/shape_matrix.py: both sides of every compile-time switch of the kernels
-               (12, 4), (13, 4), (20, 6), (23, 5), (33, 4), (40, 4), (59, 4), (60, 4)]
+               (12, 4), (13, 4), (20, 6), (23, 5), (33, 4), (40, 4), (59, 4), (60, 4),
+               # tests/test_filter_emit_gpu.py: the smallest state (one update a step: every slot of the deferred emission collapses)
+               (1, 1)]
 
 
 if __name__ == "__main__":
