@@ -425,6 +425,56 @@ MK_API int mk_innovations(mk_context *ctx, const mk_problem *prob, double *d_wor
 MK_API int mk_innovation_stats(mk_context *ctx, int64_t B, int64_t T, int64_t N, int time_major, int64_t t_first, int64_t nlags,
                                const double *d_v, const double *d_f, double *d_stats);
 
+/* MULTI-STEP-AHEAD FORECASTS and FORECAST SKILL BY HORIZON (statsmodels' forecast / get_prediction, KFAS' predict): what the model
+ * says about steps it has not seen, and how far ahead that is worth anything.  Model and units as in mk_innovations (Phi and Q
+ * diagonal, Z = [I | Gamma], observation variances R_j, zero when d_obsvar is NULL; the filter's standardised units, scale /
+ * offset applied only where said).
+ *   ORIGIN o in {-1, 0, .., T-1} has the moments (a_o, P_o): the filtered record of step o for o >= 0, the initial moments (d_x0 /
+ * d_P0, or 0 / I) for o = -1.  PROPAGATION: for h >= 1 the filter's own prediction (kalmanfilter.py:318-331) applied h times,
+ * x <- phi o x, P <- (phi phi') o P + diag(q).  FORECAST of series j: m_{o,h,j} = z_j x and s_{o,h,j} = z_j P z_j' + R_j -- the
+ * operations the filter performs on h successive empty steps, so they equal (up to rounding) the filter's predicted moments on
+ * a record whose steps after o are all missing.  One call writes any non-empty subset of three outputs:
+ *   fan     d_fan_means, d_fan_vars [B,H,N], H = horizon: row h - 1 holds m * scale + offset and max(s, 0) * scale^2 for
+ *           h = 1 .. H from the origin of the instance's RECORD, d_fan_origins[record] (int64 [n_records], values -1 .. T-1; NULL:
+ *           T - 1 for all).  The targets may lie beyond T: the out-of-sample forecast.
+ *   track   d_track_means, d_track_vars [B,T,N], or [T,B,N] with time_major, for ONE horizon track_horizon >= 1: row t is the
+ *           forecast of step t made at origin max(t - track_horizon, -1), propagated t - origin steps, scaled as above; defined at
+ *           every step, observed or not.  track_horizon = 1 gives mk_innovations' d_pred_means / d_pred_vars.
+ *   skill   d_skill [B,N,H,6]: per (instance, series j, horizon h) the sums over the pairs (o, t = o + h) with t_first <= o,
+ *           t <= T - 1 and y_{t,j} finite; with e = y_{t,j} - m_{o,h,j} and s = s_{o,h,j} the six columns are
+ *               [ m (pair count), sum e, sum e^2, sum e^2 / s, sum log s, hits ],   hits = #{ e^2 <= coverage_z^2 s },
+ *           all in the filter's units.  An origin counts whether or not step o itself was observed; without pairs all six are
+ *           exactly 0.
+ * Every sum is taken in an order fixed by T, H and t_first alone: the outputs of an instance are bit-identical whatever batch it
+ * sits in, whatever n_instances is and whichever subset of outputs is asked for.
+ *   Limits: 1 <= horizon <= mk_forecast_max_horizon() = 32, 1 <= track_horizon <= T (read only when a track output is set),
+ * t_first >= 0, coverage_z > 0 and finite.  prob->warmup is ignored; d_status (may be NULL) receives the filter's MK_FLAG_* bits
+ * -- the outputs of an instance with MK_FLAG_NONPOSITIVE_F are not meaningful.
+ *   Launches: the recording forward pass of mk_loglik_grad into d_work -- n_instances * T * mk_forecast_work_stride(N, K) doubles:
+ * the filtered full-square records packed at its head, the per-chunk partial sums of the skill table behind them -- then
+ * forecast_path_kernel (fan and track, one (instance, row) per lane group) and forecast_skill_kernel (one (instance, chunk of
+ * origins, block of horizons) per lane group; a second small kernel adds the chunks in ascending order when T exceeds one
+ * chunk), on the context's stream, timed in the smoother slot of mk_last_kernel_ms / mk_kernel_ms_totals.  The kernels read the
+ * (c, r) image of the records the specialised recording pass writes, at the same positions under the size-generic family (which
+ * writes the transpose, equal up to rounding), as innov_step_kernel does.
+ *   Served: every supported shape with N + K <= 64, under either kernel family; mk_forecast_work_stride returns 0 otherwise and
+ * mk_forecast fails with MK_ERR_SHAPE.  MK_ERR_INVALID (no launch): all outputs NULL, a missing d_work, a limit above violated, a
+ * fan origin out of range (checked on the host: n_records integers are copied back), a buffer larger than the allocation it
+ * points into. */
+typedef struct mk_forecast_request {
+    int64_t horizon, t_first, track_horizon;   /* track_horizon read only when a track output is set */
+    double coverage_z;
+    const int64_t *d_fan_origins;              /* [n_records] or NULL */
+    double *d_fan_means, *d_fan_vars;          /* [B,H,N] */
+    double *d_track_means, *d_track_vars;      /* [B,T,N] / [T,B,N] */
+    double *d_skill;                           /* [B,N,H,6] */
+} mk_forecast_request;
+
+MK_API int64_t mk_forecast_max_horizon(void);
+MK_API int64_t mk_forecast_work_stride(int64_t N, int64_t K);
+MK_API int mk_forecast(mk_context *ctx, const mk_problem *prob, double *d_work, int time_major, const mk_forecast_request *req,
+                       uint32_t *d_status);
+
 /* Posterior DRAWS of the states and of the projected series: the simulation smoother by mean correction (Durbin & Koopman 2002,
  * Biometrika 89:603-616).  For the model the filter implements (seqkalmanfilter, metran/kalmanfilter.py:315-333:
  * x_{-1} ~ N(x0, P0), x_t = phi o x_{t-1} + w_t, y_t = [I | Gamma] x_t + e_t) and path id = s * n_instances + i (draw s of instance i,

@@ -8,7 +8,7 @@ import ctypes
 import os
 from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
 
-__all__ = ["MetranHipError", "lib", "library_path", "Problem", "Outputs", "check", "API"]
+__all__ = ["MetranHipError", "lib", "library_path", "Problem", "Outputs", "ForecastRequest", "check", "API"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIBNAME = "libmetran_hip.so"
@@ -67,6 +67,23 @@ class Outputs(Structure):
         ("d_sim_vars", c_void_p),
         ("record_stride", c_int64),
         ("flags", c_int64),
+    ]
+
+
+class ForecastRequest(Structure):
+    """``mk_forecast_request`` (include/metran_hip.h)."""
+
+    _fields_ = [
+        ("horizon", c_int64),
+        ("t_first", c_int64),
+        ("track_horizon", c_int64),
+        ("coverage_z", c_double),
+        ("d_fan_origins", c_void_p),
+        ("d_fan_means", c_void_p),
+        ("d_fan_vars", c_void_p),
+        ("d_track_means", c_void_p),
+        ("d_track_vars", c_void_p),
+        ("d_skill", c_void_p),
     ]
 
 
@@ -136,6 +153,9 @@ API = {
     "mk_innovations_work_stride": (c_int64, [c_int64, c_int64]),
     "mk_innovations": (c_int, [c_void_p, POINTER(Problem), c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mk_innovation_stats": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "mk_forecast_max_horizon": (c_int64, []),
+    "mk_forecast_work_stride": (c_int64, [c_int64, c_int64]),
+    "mk_forecast": (c_int, [c_void_p, POINTER(Problem), c_void_p, c_int, POINTER(ForecastRequest), c_void_p]),
     "mk_draw_perturb": (c_int, [c_void_p, POINTER(Problem), c_uint64, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p,
                                 c_void_p]),
     "mk_draw_combine": (c_int, [c_void_p, POINTER(Problem), c_int64, c_int, c_int, c_void_p, c_void_p]),

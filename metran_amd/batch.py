@@ -11,6 +11,8 @@ number comes from the HIP kernels:
     loo_predict              ->  leave-one-out predictions of every observation (get_loo_simulation, get_deletion_residuals)
     smooth_state_variances   ->  state means / variances / decomposition
     disturbances             ->  smoothed state disturbances and auxiliary residuals (get_auxiliary_residuals, screen_breaks)
+    forecast                 ->  multi-step-ahead forecasts and forecast skill by horizon (get_forecast, get_prediction_at,
+                                 forecast_skill)
 
 Results of the last filter / smoother run are cached per parameter set, like ``Metran._run_kalman`` does
 (metran.py:963-989): asking for another series, the variances after the means, or the decomposition after the
@@ -311,6 +313,108 @@ class MetranBatch:
                            "pvalue": chi2.sf(flat[:, 3], nlags)}, index=index)
         for l in range(1, nlags + 1):
             frame["r%d" % l] = flat[:, 3 + l]
+        return frame
+
+    # ------------------------------------------------------------------ multi-step-ahead forecasts and their skill
+    def _forecast(self, alpha, outputs, horizon=1, track_horizon=1, t_first=1, coverage=0.95):
+        """``BatchedKalman.forecast`` for the parameter set: the cached kind "forecast", one result per REQUEST (outputs,
+        horizon, track horizon, first origin, coverage) of the parameter set it was computed with; fan and track in ORIGINAL
+        units, the fan from every model's last real step (``lengths[r] - 1``: shorter records are padded with empty steps)."""
+        import torch
+
+        from .kalmanfilter import check_status
+
+        a = self._alpha(alpha)
+        request = (tuple(outputs), int(horizon), int(track_horizon), int(t_first), float(coverage))
+        hit = self._cache.get("forecast")
+        if hit is None or hit[0].shape != a.shape or not bool(torch.equal(hit[0], a)):
+            hit = self._cache["forecast"] = (a.clone(), {})
+        if request not in hit[1]:
+            phi, q = self.kf.params_from_alpha(a, dt=self.dt)
+            self.kf.set_scaling(self._std, self._mean)
+            out = self.kf.forecast(phi, q, horizon=request[1], outputs=request[0], origins=np.asarray(self.batch.lengths, dtype=np.int64) - 1,
+                                   track_horizon=request[2], t_first=request[3], coverage=request[4])
+            check_status(out["status"], "MetranBatch(forecast)")
+            # the forward pass's workspace (the records: hundreds of times the outputs) is not kept: one entry per request
+            hit[1][request] = {k: v for k, v in out.items() if k != "_work"}
+        return hit[1][request]
+
+    def _forecast_moments(self, steps, alpha, standardized):
+        out = self._forecast(alpha, ("fan",), horizon=steps)
+        means, variances = out["fan_mean"], out["fan_var"]
+        if standardized:
+            means = (means - self._mean[:, None, :]) / self._std[:, None, :]
+            variances = variances / (self._std * self._std)[:, None, :]
+        return means, variances
+
+    def get_forecast_means(self, steps=14, alpha=None, standardized=False):
+        """OUT-OF-SAMPLE forecast means ``[R,steps,N]``: row h - 1 is the forecast of every series h steps after the model's
+        last real step (``lengths[r] - 1``), from all of its observations."""
+        return self._forecast_moments(steps, alpha, standardized)[0]
+
+    def get_forecast_variances(self, steps=14, alpha=None, standardized=False):
+        """The variances ``[R,steps,N]`` of ``get_forecast_means``: those of the OBSERVATION (projected state variance plus
+        observation variance)."""
+        return self._forecast_moments(steps, alpha, standardized)[1]
+
+    def get_forecast(self, r, name, steps=14, alpha=None, ci=0.05, standardized=False):
+        """The forecast of series ``name`` of model ``r`` over the ``steps`` days after the model's last real step: DataFrame
+        (``mean``, ``lower``, ``upper``) whose index continues the record's daily index; the band is that of the OBSERVATION, as
+        in ``get_prediction``.  ``ci=None`` returns the mean Series."""
+        from pandas import Series, Timedelta, date_range
+
+        j = self._series(r, name)
+        means, variances = self._forecast_moments(steps, alpha, standardized)
+        index = date_range(self.batch.index[r][-1] + Timedelta(days=1), periods=int(steps), freq="D")
+        mean = Series(means[r, :, j].cpu().numpy(), index=index, name=name)
+        return self._band(mean, Series(variances[r, :, j].cpu().numpy(), index=index, name=name) if ci is not None else None, ci)
+
+    def get_prediction_at(self, r, name, horizon, alpha=None, ci=0.05, standardized=False):
+        """The ``horizon``-STEP-AHEAD counterpart of ``get_prediction``: DataFrame (``mean``, ``lower``, ``upper``) of the forecast
+        of series ``name`` of model ``r`` at every step t made ``horizon`` steps earlier, from the observations up to step
+        t - horizon alone (from the initial state where t < horizon) -- what one plots against the observations to see how
+        far ahead the model is worth anything.  ``horizon=1`` is ``get_prediction``."""
+        j = self._series(r, name)
+        out = self._forecast(alpha, ("track",), track_horizon=horizon)  # original units
+        means, variances = out["track_mean"], out["track_var"]
+        if standardized:
+            means = (means - self._mean[:, None, :]) / self._std[:, None, :]
+            variances = variances / (self._std * self._std)[:, None, :]
+        L = int(self.batch.lengths[r])
+        sim = self.batch.frame(r, means[r].cpu().numpy()).iloc[:L, j]
+        return self._band(sim, self.batch.frame(r, variances[r].cpu().numpy()).iloc[:L, j] if ci is not None else None, ci)
+
+    def forecast_skill(self, horizon=14, alpha=None, t_first=1, coverage=0.95):
+        """Forecast skill by horizon, the out-of-sample counterpart of ``test_whiteness``: DataFrame indexed (model, series,
+        horizon) over the pairs (origin o, target t = o + h) with ``o >= t_first`` and the series observed at t, every
+        forecast made from the observations up to o alone (parameters held fixed): ``nobs``; ``bias`` = mean error and ``rmse``
+        in ORIGINAL units; ``msse`` = mean of e^2 / s (about 1 for an adequate model: the bands are honest); ``logscore`` =
+        -(log 2 pi + mean log s + msse) / 2 in standardised units; ``coverage`` = the share of the pairs inside the central
+        ``coverage`` band, beside ``nominal``; ``skill`` = 1 - mse / var, var the variance of the series' standardised
+        observations: the gain over predicting the series' mean.  NaN where ``nobs`` = 0.  Padding steps of a shorter record
+        are empty and add no pairs."""
+        import torch
+        from pandas import DataFrame, MultiIndex
+
+        horizon = int(horizon)
+        out = self._forecast(alpha, ("skill",), horizon=horizon, t_first=t_first, coverage=coverage)
+        s = out["skill"].cpu().numpy().reshape(self.R * self.N, horizon, 6)
+        obs = self.kf.obs
+        seen = torch.isfinite(obs)
+        cnt = seen.sum(1).to(obs.dtype)
+        mean = torch.where(seen, obs, torch.zeros_like(obs)).sum(1) / cnt
+        var = (torch.where(seen, obs - mean[:, None, :], torch.zeros_like(obs)) ** 2).sum(1) / cnt   # [R,N], divisor m
+        var = np.repeat(var.cpu().numpy().reshape(-1), horizon)
+        std = np.repeat(self._std.cpu().numpy().reshape(-1), horizon)
+        index = MultiIndex.from_tuples([(r + self.shard[0], name, h) for r in range(self.R) for name in self.batch.names[r]
+                                        for h in range(1, horizon + 1)], names=["model", "series", "horizon"])
+        flat = s.reshape(-1, 6)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            m = np.where(flat[:, 0] > 0, flat[:, 0], np.nan)
+            mse, msse = flat[:, 2] / m, flat[:, 3] / m
+            frame = DataFrame({"nobs": flat[:, 0].astype(np.int64), "bias": flat[:, 1] / m * std, "rmse": np.sqrt(mse) * std, "msse": msse,
+                               "logscore": -0.5 * (np.log(2.0 * np.pi) + flat[:, 4] / m + msse), "coverage": flat[:, 5] / m,
+                               "nominal": np.where(np.isnan(m), np.nan, float(coverage)), "skill": 1.0 - mse / var}, index=index)
         return frame
 
     # ------------------------------------------------------------------ state disturbances (break detection)

@@ -3,6 +3,7 @@
 // mk_status translation, optional hipEvent timing of the two hot kernels.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -12,6 +13,7 @@
 #include <new>
 
 #include "draw_kernels.h"
+#include "forecast_kernels.h"
 #include "innov_kernels.h"
 #include "mk_generic.h"
 #include "mk_internal.h"
@@ -1395,6 +1397,111 @@ MK_API int mk_innovation_stats(mk_context *ctx, int64_t B, int64_t T, int64_t N,
     a.f = d_f;
     a.stats = d_stats;
     MK_HIP(mk::launch_innov_stats(a, ctx->stream));
+    return MK_OK;
+}
+
+// ---- multi-step-ahead forecasts and forecast skill by horizon (forecast_kernels.hip) ----
+MK_API int64_t mk_forecast_max_horizon(void) { return mk::forecast_max_horizon; }
+
+MK_API int64_t mk_forecast_work_stride(int64_t N, int64_t K)
+{
+    if (N < 1 || K < 1 || N + K > mk::forecast_max_states || !mk_shape_supported(N, K)) return 0;
+    return mk::record_stride((int)(N + K)) + mk::forecast_partial_stride(N);
+}
+
+MK_API int mk_forecast(mk_context *ctx, const mk_problem *p, double *d_work, int time_major, const mk_forecast_request *req,
+                       uint32_t *d_status)
+{
+    MK_CTX(ctx);
+    if (p && p->N >= 1 && p->K >= 1 && p->N + p->K > mk::forecast_max_states)
+        return fail(MK_ERR_SHAPE, "mk_forecast serves N + K <= %d states (got N=%lld, K=%lld)", mk::forecast_max_states, (long long)p->N,
+                    (long long)p->K);
+    if (int rc = check_problem(p)) return rc;
+    if (!req) return fail(MK_ERR_INVALID, "mk_forecast: null mk_forecast_request");
+    if (!d_work) return fail(MK_ERR_INVALID, "mk_forecast: d_work is required");
+    const bool fan = req->d_fan_means || req->d_fan_vars, track = req->d_track_means || req->d_track_vars, skill = req->d_skill != nullptr;
+    if (!fan && !track && !skill)
+        return fail(MK_ERR_INVALID, "mk_forecast: nothing to write, give one of d_fan_means, d_fan_vars, d_track_means, d_track_vars, d_skill");
+    if (!p->d_obs || !p->d_loadings) return fail(MK_ERR_INVALID, "d_obs and d_loadings are required");
+    if (req->horizon < 1 || req->horizon > mk::forecast_max_horizon)
+        return fail(MK_ERR_INVALID, "mk_forecast: need 1 <= horizon <= %d (got %lld)", mk::forecast_max_horizon, (long long)req->horizon);
+    if (track && (req->track_horizon < 1 || req->track_horizon > p->T))
+        return fail(MK_ERR_INVALID, "mk_forecast: need 1 <= track_horizon <= T = %lld (got %lld)", (long long)p->T,
+                    (long long)req->track_horizon);
+    if (req->t_first < 0) return fail(MK_ERR_INVALID, "mk_forecast: t_first must be >= 0");
+    if (!(req->coverage_z > 0.0) || !std::isfinite(req->coverage_z))
+        return fail(MK_ERR_INVALID, "mk_forecast: coverage_z must be positive and finite");
+    const int64_t ws = mk_forecast_work_stride(p->N, p->K);
+    if (!ws)
+        return fail(MK_ERR_SHAPE, "mk_forecast serves N + K <= %d states (got N=%lld, K=%lld)", mk::forecast_max_states, (long long)p->N,
+                    (long long)p->K);
+    const int64_t n = p->N + p->K, B = p->n_instances, rs = mk::record_stride((int)n);
+    const draw_buffer bufs[7] = {{d_work, B * p->T * ws, "d_work (n_instances * T * mk_forecast_work_stride(N, K) doubles)"},
+                                 {req->d_fan_origins, p->n_records, "d_fan_origins (n_records 64-bit integers)"},
+                                 {req->d_fan_means, B * req->horizon * p->N, "d_fan_means (n_instances * horizon * N doubles)"},
+                                 {req->d_fan_vars, B * req->horizon * p->N, "d_fan_vars (n_instances * horizon * N doubles)"},
+                                 {req->d_track_means, B * p->T * p->N, "d_track_means (n_instances * T * N doubles)"},
+                                 {req->d_track_vars, B * p->T * p->N, "d_track_vars (n_instances * T * N doubles)"},
+                                 {req->d_skill, B * p->N * req->horizon * 6, "d_skill (n_instances * N * horizon * 6 doubles)"}};
+    if (int rc = draw_buffers_fit("mk_forecast", bufs, 7)) return rc;
+    if (fan && req->d_fan_origins) { // R integers to the host: an origin out of range would index outside the records
+        std::vector<int64_t> h((size_t)p->n_records);
+        MK_HIP(hipMemcpyAsync(h.data(), req->d_fan_origins, sizeof(int64_t) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
+        MK_HIP(hipStreamSynchronize(ctx->stream));
+        for (int64_t r = 0; r < p->n_records; ++r)
+            if (h[(size_t)r] < -1 || h[(size_t)r] > p->T - 1)
+                return fail(MK_ERR_INVALID, "mk_forecast: d_fan_origins[%lld] = %lld is outside -1 .. T - 1 = %lld", (long long)r,
+                            (long long)h[(size_t)r], (long long)(p->T - 1));
+    }
+    // the recording forward pass of mk_loglik_grad: filtered records only (+ the per-step bookkeeping in the record pads), packed
+    // at the head of d_work; the skill kernel's partial sums live behind them
+    mk_outputs o;
+    memset(&o, 0, sizeof(o));
+    o.d_status = d_status;
+    o.d_F = d_work;
+    o.d_Pf = d_work + n;
+    o.d_sigmas = d_work + n + n * n;
+    o.d_detfs = o.d_sigmas + 1;
+    o.time_major = time_major;
+    o.record_stride = rs;
+    if (int rc = do_filter(ctx, p, &o)) return rc;
+    mk::ForecastArgs a;
+    memset(&a, 0, sizeof(a));
+    a.B = B;
+    a.R = p->n_records;
+    a.T = p->T;
+    a.N = (int)p->N;
+    a.K = (int)p->K;
+    a.H = (int)req->horizon;
+    a.track_h = track ? req->track_horizon : 1;
+    a.t_first = req->t_first;
+    a.bs = time_major ? 1 : p->T;
+    a.ts = time_major ? B : 1;
+    a.rs = rs;
+    a.obs_bs = p->obs_time_major ? 1 : p->T;
+    a.obs_ts = p->obs_time_major ? p->n_records : 1;
+    a.z2 = req->coverage_z * req->coverage_z;
+    a.obs = p->d_obs;
+    a.phi = p->d_phi;
+    a.q = p->d_q;
+    a.loadings = p->d_loadings;
+    a.obsvar = p->d_obsvar;
+    a.x0 = p->d_x0;
+    a.P0 = p->d_P0;
+    a.scale = p->d_scale;
+    a.offset = p->d_offset;
+    a.F = d_work;
+    a.fan_origins = req->d_fan_origins;
+    a.fan_mean = req->d_fan_means;
+    a.fan_var = req->d_fan_vars;
+    a.track_mean = req->d_track_means;
+    a.track_var = req->d_track_vars;
+    a.skill = req->d_skill;
+    a.partial = d_work + B * p->T * rs;
+    MK_HIP(timing_start(ctx, 1));
+    if (fan || track) MK_HIP(mk::launch_forecast_path(a, ctx->stream));
+    if (skill) MK_HIP(mk::launch_forecast_skill(a, ctx->stream));
+    MK_HIP(timing_stop(ctx, 1)); // reported in the smoother slot of mk_last_kernel_ms / mk_kernel_ms_totals
     return MK_OK;
 }
 

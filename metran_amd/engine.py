@@ -14,7 +14,7 @@ import logging
 import numpy as np
 
 from . import _lib
-from ._lib import MetranHipError, Outputs, Problem, check
+from ._lib import ForecastRequest, MetranHipError, Outputs, Problem, check
 
 logger = logging.getLogger(__name__)
 
@@ -864,6 +864,107 @@ class BatchedKalman:
         check(self._L.mk_innovation_stats(self._ctx, B, T, N, 1 if self.time_major else 0, t_first, nlags, self._p(v), self._p(f),
                                           self._p(stats)))
         return stats
+
+    # ------------------------------------------------------------------ multi-step-ahead forecasts and forecast skill
+    _FORECAST_OUTPUTS = ("fan", "track", "skill")
+
+    @property
+    def forecast_supported(self):
+        """True when ``forecast`` serves this engine's shape (C ABI ``mk_forecast_work_stride`` > 0): N + K <= 64,
+        specialised or size-generic kernels alike."""
+        return self.loadings is not None and int(self._L.mk_forecast_work_stride(self.N, self.K)) > 0
+
+    def _forecast_stride(self):
+        if not self.forecast_supported:
+            raise MetranHipError("forecasts serve shapes with N + K <= 64; (N=%s, K=%s) is not one" % (self.N, getattr(self, "K", None)))
+        return int(self._L.mk_forecast_work_stride(self.N, self.K))
+
+    def _forecast_shapes(self, B, horizon, outputs):
+        """name -> (logical shape, follows the engine's layout) of the buffers of ``forecast``."""
+        shapes = {"_work": ((B, self.T, self._forecast_stride()), True)}
+        if "fan" in outputs:
+            shapes["fan_mean"] = shapes["fan_var"] = ((B, horizon, self.N), False)
+        if "track" in outputs:
+            shapes["track_mean"] = shapes["track_var"] = ((B, self.T, self.N), True)
+        if "skill" in outputs:
+            shapes["skill"] = ((B, self.N, horizon, 6), False)
+        return shapes
+
+    def _forecast_request(self, horizon, outputs):
+        outputs = tuple(outputs)
+        if not outputs or any(k not in self._FORECAST_OUTPUTS for k in outputs):
+            raise ValueError("outputs must be a non-empty subset of %s" % (self._FORECAST_OUTPUTS,))
+        horizon = int(horizon)
+        if not 1 <= horizon <= int(self._L.mk_forecast_max_horizon()):
+            raise ValueError("horizon must be in 1..%d" % int(self._L.mk_forecast_max_horizon()))
+        return horizon, outputs
+
+    def alloc_forecast(self, B, horizon=14, outputs=("fan", "skill")):
+        """Buffers of ``forecast`` for B instances (the forward pass's workspace + the outputs asked for), for callers that run
+        it repeatedly (pass them back as ``buffers=``)."""
+        torch = _torch()
+        horizon, outputs = self._forecast_request(horizon, outputs)
+        res = {"status": torch.zeros(B, dtype=torch.int32, device=self.device)}
+        for key, (shape, bt) in self._forecast_shapes(B, horizon, outputs).items():
+            res[key] = self._empty_bt(*shape) if bt else torch.empty(shape, dtype=torch.float64, device=self.device)
+        return res
+
+    def forecast(self, phi, q, x0=None, P0=None, horizon=14, outputs=("fan", "skill"), origins=None, track_horizon=1, t_first=1,
+                 coverage=0.95, buffers=None):
+        """MULTI-STEP-AHEAD forecasts and forecast skill for B instances (C ABI ``mk_forecast``).  From an ORIGIN o -- the
+        filtered moments of step o, or the initial moments for o = -1 -- the filter's prediction applied h times gives the
+        forecast of every series h steps ahead, mean and variance (observation variance included).  ``outputs``:
+
+        ``"fan"``    ``fan_mean, fan_var [B,horizon,N]``: h = 1 .. horizon from the origin of the instance's record, ``origins``
+                     (``[R]`` integers in -1 .. T-1; None = T - 1, the out-of-sample forecast), in the units of ``set_scaling``;
+        ``"track"``  ``track_mean, track_var [B,T,N]``: at every step t the forecast made ``track_horizon`` steps earlier (from the
+                     initial moments where t < track_horizon), in the units of ``set_scaling``; ``track_horizon=1`` is
+                     ``innovations``' ``pred_mean / pred_var``;
+        ``"skill"``  ``skill [B,N,horizon,6]``: per series and horizon h, over the pairs (o, t = o + h) with ``t_first <= o``, t < T
+                     and y[t] observed, ``[count, sum e, sum e^2, sum e^2/s, sum log s, hits]`` of e = y - mean, s = variance, in the
+                     filter's units; hits counts e^2 <= z^2 s with z the two-sided normal quantile of ``coverage``.
+
+        Returns a dict with those tensors and ``status`` (the filter's MK_FLAG_* bits); the rows of an instance whose status
+        carries ``FLAG_NONPOSITIVE_F`` are NaN.  Every sum has a fixed order: an instance's rows do not depend on the batch."""
+        from scipy.stats import norm
+
+        torch = _torch()
+        horizon, outputs = self._forecast_request(horizon, outputs)
+        track_horizon, t_first, coverage = int(track_horizon), int(t_first), float(coverage)
+        if "track" in outputs and not 1 <= track_horizon <= self.T:
+            raise ValueError("track_horizon must be in 1..T = %d" % self.T)
+        if t_first < 0:
+            raise ValueError("t_first must be >= 0")
+        if not 0.0 < coverage < 1.0:
+            raise ValueError("coverage must be in (0, 1)")
+        self._forecast_stride()
+        prob, keep, B = self._problem(phi, q, 0, x0, P0)
+        res = buffers if buffers is not None else self.alloc_forecast(B, horizon, outputs)
+        shapes = self._forecast_shapes(B, horizon, outputs)
+        for key, (shape, bt) in shapes.items():
+            t = res.get(key)
+            if t is None or tuple(t.shape) != shape or not ((self._layout(t) is t) if bt else t.is_contiguous()):
+                raise ValueError("buffers[%r] must be a %s tensor%s (alloc_forecast)" % (key, list(shape), " in the engine's layout" if bt else ""))
+        org = None
+        if origins is not None and "fan" in outputs:
+            org = torch.as_tensor(origins, dtype=torch.int64).reshape(-1).to(self.device).contiguous()
+            if org.numel() != self.R:
+                raise ValueError("origins must hold one origin per record (%d)" % self.R)
+        req = ForecastRequest()
+        req.horizon, req.t_first, req.track_horizon = horizon, t_first, track_horizon
+        req.coverage_z = float(norm.ppf(0.5 + 0.5 * coverage))
+        req.d_fan_origins = None if org is None else org.data_ptr()
+        for field, key in (("d_fan_means", "fan_mean"), ("d_fan_vars", "fan_var"), ("d_track_means", "track_mean"),
+                           ("d_track_vars", "track_var"), ("d_skill", "skill")):
+            setattr(req, field, res[key].data_ptr() if key in shapes else None)
+        self._bind_stream()
+        check(self._L.mk_forecast(self._ctx, ctypes.byref(prob), self._p(res["_work"]), 1 if self.time_major else 0, ctypes.byref(req),
+                                  self._p(res["status"])))
+        bad = (res["status"] & FLAG_NONPOSITIVE_F) != 0
+        for key in shapes:
+            if key != "_work":
+                res[key].masked_fill_(bad.view((B,) + (1,) * (res[key].ndim - 1)), float("nan"))
+        return res
 
     # ------------------------------------------------------------------ posterior draws (simulation smoother)
     def _draw_perturb(self, prob, B, ndraws, seed, first_instance, first_draw, antithetic, L0, want_zx, want_x):
