@@ -37,18 +37,12 @@
 #include <cmath>
 
 #include "forecast_kernels.h"
+#include "mk_prims.h" // wave_lds_sync
+#include "reader_prims.h"
 
 namespace mk {
 
 namespace {
-
-// the lanes of ONE wavefront exchange data through LDS: program order of the LDS instructions is all that is needed
-__device__ __forceinline__ void fc_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-}
 
 // doubles of LDS per lane group: phi, q and the means of the factors (3 K), the factor block (K x K), the loadings and the
 // series-factor covariances, both as K columns of G lanes
@@ -81,7 +75,7 @@ struct FcState {
     // the moments of origin o: position (c, r) of the record's square is lane r's column c (see the header comment)
     __device__ __forceinline__ void load(const ForecastArgs &a, long b, long o)
     {
-        fc_lds_sync(); // the reads of the previous origin are done
+        wave_lds_sync(); // the reads of the previous origin are done
         if (o >= 0) {
             const double *p = a.F + (b * a.bs + o * a.ts) * a.rs;
             x = p[jl];
@@ -108,7 +102,7 @@ struct FcState {
                 PF[i] = a.P0 ? a.P0[(b * n + N + k) * n + N + l] : (k == l ? 1.0 : 0.0);
             }
         }
-        fc_lds_sync();
+        wave_lds_sync();
     }
 
     // one prediction (:318-331; Phi diagonal): x = phi o x, P = (phi phi') o P + diag(q) -- innov_step_kernel's multiply-adds
@@ -125,7 +119,7 @@ struct FcState {
             const int k = i / K, l = i - k * K;
             PF[i] = fma(PF[i], phf[k] * phf[l], k == l ? qf[k] : 0.0);
         }
-        fc_lds_sync();
+        wave_lds_sync();
     }
 
     // m = z_j x and s = z_j P z_j' + r_j, Z = [I | loadings]; the caller syncs before the next predict()
@@ -198,11 +192,11 @@ __global__ void __launch_bounds__(256) forecast_path_kernel(ForecastArgs a)
             const long orow = fan ? (b * a.H + (h - 1)) * a.N + lane : (b * a.bs + t * a.ts) * a.N + lane;
             double *om = fan ? a.fan_mean : a.track_mean, *ov = fan ? a.fan_var : a.track_var;
             if (store) {
-                if (om) om[orow] = fma(pm, sc, of);
-                if (ov) ov[orow] = (pv < 0.0 ? 0.0 : pv) * sc * sc;
+                if (om) om[orow] = scaled_mean(pm, sc, of);
+                if (ov) ov[orow] = scaled_var(pv, sc);
             }
         }
-        fc_lds_sync();
+        wave_lds_sync();
     }
 }
 
@@ -269,7 +263,7 @@ __global__ void __launch_bounds__(256) forecast_skill_kernel(ForecastArgs a)
                 FC_ADD(0) FC_ADD(1) FC_ADD(2) FC_ADD(3) FC_ADD(4) FC_ADD(5) FC_ADD(6) FC_ADD(7)
             }
 #undef FC_ADD
-            fc_lds_sync();
+            wave_lds_sync();
         }
     }
 

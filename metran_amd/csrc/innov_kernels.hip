@@ -27,28 +27,12 @@
 #include <cmath>
 
 #include "innov_kernels.h"
+#include "mk_prims.h" // wave_lds_sync, rcp_nr: the filter kernels' own -- v and f are the filter's numbers bit for bit
+#include "reader_prims.h"
 
 namespace mk {
 
 namespace {
-
-// the lanes of ONE wavefront exchange data through LDS: program order of the LDS instructions is all that is needed
-// (LDS-only fences: a generic fence would also pin private arrays to scratch memory)
-__device__ __forceinline__ void innov_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
-}
-
-// 1 / x exactly as the filter kernels form it (mk_prims.h rcp_nr): v_rcp_f64 and one cubically convergent step
-__device__ __forceinline__ double innov_rcp(double x)
-{
-    const double r0 = __builtin_amdgcn_rcp(x);
-    const double e = fma(-x, r0, 1.0);
-    const double p = fma(e, e, e);
-    return fma(r0, p, r0);
-}
 
 // doubles of LDS per lane group: six W-vectors (z_j, d, x, phi, y, obsvar), the factor block of P (K x K) and the loadings (N x K)
 inline long innov_lds_doubles(int W, int N, int K) { return (6L * W + (long)(N + K) * K + 1) & ~1L; }
@@ -136,7 +120,7 @@ __global__ void __launch_bounds__(G == 16 ? 256 : 64) innov_step_kernel(InnovArg
             }
         }
     }
-    innov_lds_sync();
+    wave_lds_sync();
 
     // ---- predict (:318-331; Phi diagonal): x = phi o x, P = (phi phi') o P + diag(q)
     x = phi_r * x;
@@ -157,7 +141,7 @@ __global__ void __launch_bounds__(G == 16 ? 256 : 64) innov_step_kernel(InnovArg
             if (c >= N && c < n) {
                 if (act && !ser) PF[(lane - N) * K + (c - N)] = P[c];
             }
-        innov_lds_sync();
+        wave_lds_sync();
         double diag = 0.0, cross = 0.0, pm = x;
 #pragma unroll
         for (int c = 0; c < W; ++c) {
@@ -177,8 +161,8 @@ __global__ void __launch_bounds__(G == 16 ? 256 : 64) innov_step_kernel(InnovArg
         const double pv = fma(2.0, cross, diag) + quad + rv[jl];
         const double sc = a.scale ? a.scale[rec * N + jl] : 1.0, of = a.offset ? a.offset[rec * N + jl] : 0.0;
         if (live && ser) {
-            if (a.pred_mean) a.pred_mean[orow] = fma(pm, sc, of);
-            if (a.pred_var) a.pred_var[orow] = (pv < 0.0 ? 0.0 : pv) * sc * sc;
+            if (a.pred_mean) a.pred_mean[orow] = scaled_mean(pm, sc, of);
+            if (a.pred_var) a.pred_var[orow] = scaled_var(pv, sc);
         }
     }
     if (!(a.v || a.f)) return;
@@ -186,14 +170,14 @@ __global__ void __launch_bounds__(G == 16 ? 256 : 64) innov_step_kernel(InnovArg
     // ---- sequential scalar updates (:341-378), ascending series order over the observed series
     double vown = nan, fown = nan;
     for (int j = 0; j < N; ++j) {
-        innov_lds_sync();
+        wave_lds_sync();
         const double y = yv[j];
         if (!isfinite(y)) continue; // NaN / inf = missing (:657); the same for every lane of the group
         if (lane < W) {
             zv[lane] = ser ? (lane == j ? 1.0 : 0.0) : (act ? Gm[j * K + (lane - N)] : 0.0);
             xv[lane] = act ? x : 0.0;
         }
-        innov_lds_sync();
+        wave_lds_sync();
         double d = 0.0, v = y; // d_r = (P z_j')_r (:349-357), v = y - z_j x (:344-347)
 #pragma unroll
         for (int c0 = 0; c0 < W; c0 += 4) {
@@ -207,7 +191,7 @@ __global__ void __launch_bounds__(G == 16 ? 256 : 64) innov_step_kernel(InnovArg
             }
         }
         if (lane < W) dv[lane] = act ? d : 0.0;
-        innov_lds_sync();
+        wave_lds_sync();
         double f = rv[j]; // f = z_j d + r_j (:359-362)
 #pragma unroll
         for (int c0 = 0; c0 < W; c0 += 4) {
@@ -216,7 +200,7 @@ __global__ void __launch_bounds__(G == 16 ? 256 : 64) innov_step_kernel(InnovArg
                 for (int c = c0; c < c0 + 4; ++c) f = fma(zv[c], dv[c], f);
             }
         }
-        const double rf = innov_rcp(f), kr = d * rf;
+        const double rf = rcp_nr(f), kr = d * rf;
 #pragma unroll
         for (int c0 = 0; c0 < W; c0 += 4) { // P -= k k' f (:368-372)
             if (c0 < n) {
@@ -284,7 +268,7 @@ __global__ void __launch_bounds__(256) innov_stats_kernel(InnovStatsArgs a)
         const unsigned long long ball = __ballot(ok);
         const int pos = __popcll(ball & ((1ull << lane) - 1ull)), cnt = __popcll(ball);
         if (ok) buf[innov_max_lags + pos] = e - mean;
-        innov_lds_sync();
+        wave_lds_sync();
         if (lane < cnt) {
             const double own = buf[innov_max_lags + lane];
             const long gi = base + lane;
@@ -294,11 +278,11 @@ __global__ void __launch_bounds__(256) innov_stats_kernel(InnovStatsArgs a)
                     if (gi >= l) acc[l] = fma(own, buf[innov_max_lags + lane - l], acc[l]);
                 }
         }
-        innov_lds_sync();
+        wave_lds_sync();
         const double keep = lane < innov_max_lags ? buf[cnt + lane] : 0.0; // the last innov_max_lags values move to the front
-        innov_lds_sync();
+        wave_lds_sync();
         if (lane < innov_max_lags) buf[lane] = keep;
-        innov_lds_sync();
+        wave_lds_sync();
         base += cnt;
     }
 #pragma unroll

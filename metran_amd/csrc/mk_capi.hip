@@ -186,6 +186,68 @@ hipError_t dispatch_smoother(mk_context *ctx, int N, int K, const mk::SmootherAr
 }
 } // namespace
 
+// ---- what the kernels' argument blocks share, filled from mk_problem.  FilterArgs, AdjointArgs, InnovArgs, ForecastArgs and DrawArgs
+// spell these fields alike (SparseArgs and SmootherArgs a part of them); the structs themselves stay apart, because a kernel that
+// takes its block by value is compiled against that block's layout ----
+template <class Args>
+static void fill_model(Args &a, const mk_problem *p) // sizes, observation strides, model pointers
+{
+    a.B = p->n_instances;
+    a.R = p->n_records;
+    a.T = p->T;
+    a.obs_bs = p->obs_time_major ? 1 : p->T;
+    a.obs_ts = p->obs_time_major ? p->n_records : 1;
+    a.obs = p->d_obs;
+    a.phi = p->d_phi;
+    a.q = p->d_q;
+    a.loadings = p->d_loadings;
+    a.obsvar = p->d_obsvar;
+}
+template <class Args>
+static void fill_initial(Args &a, const mk_problem *p)
+{
+    a.x0 = p->d_x0;
+    a.P0 = p->d_P0;
+}
+template <class Args>
+static void fill_scaling(Args &a, const mk_problem *p)
+{
+    a.scale = p->d_scale;
+    a.offset = p->d_offset;
+}
+template <class Args>
+static void fill_layout(Args &a, int time_major, int64_t B, int64_t T) // block (b, t) at b*bs + t*ts
+{
+    a.bs = time_major ? 1 : T;
+    a.ts = time_major ? B : 1;
+}
+
+// Each buffer must end inside the device allocation it starts in (an interior pointer of a pooled allocation passes whenever the
+// pool's block is large enough -- the check catches a buffer that is too small, not every misuse).
+struct device_buffer { const void *ptr; int64_t doubles; const char *name; };
+static int buffers_fit(const char *who, const device_buffer *bufs, int count)
+{
+    for (int k = 0; k < count; ++k) {
+        const device_buffer &b = bufs[k];
+        if (!b.ptr) continue;
+        hipDeviceptr_t base = nullptr;
+        size_t bytes = 0;
+        if (hipMemGetAddressRange(&base, &bytes, (hipDeviceptr_t)b.ptr) != hipSuccess) {
+            (void)hipGetLastError(); // not a hipMalloc allocation: its size cannot be known here
+            continue;
+        }
+        if ((const char *)b.ptr + b.doubles * (int64_t)sizeof(double) > (const char *)base + bytes)
+            return fail(MK_ERR_INVALID, "%s: %s is larger than the device allocation it points into", who, b.name);
+    }
+    return MK_OK;
+}
+
+// the refusal of the entry points whose kernels hold one state per lane
+static int too_many_states(const char *who, const mk_problem *p, int max_states)
+{
+    return fail(MK_ERR_SHAPE, "%s serves N + K <= %d states (got N=%lld, K=%lld)", who, max_states, (long long)p->N, (long long)p->K);
+}
+
 extern "C" {
 
 MK_API int mk_register_shape_module(const char *path)
@@ -663,8 +725,7 @@ static int sparse_route(mk_context *ctx, const mk_problem *p, double *d_mle, dou
     a.q = p->d_q;
     a.loadings = p->d_loadings;
     a.obsvar = p->d_obsvar;
-    a.x0 = p->d_x0;
-    a.P0 = p->d_P0;
+    fill_initial(a, p);
     a.tlist = ctx->tlist;
     a.rebuild = !(ctx->tlist_obs == p->d_obs && ctx->tlist_T == p->T && ctx->tlist_N == p->N && ctx->tlist_ostep == a.ostep);
     // the list is only known to describe this record once the launch that (re)builds it has been accepted: the key
@@ -676,8 +737,7 @@ static int sparse_route(mk_context *ctx, const mk_problem *p, double *d_mle, dou
     a.F = d_F;
     a.Xp = d_Xp;
     a.rs = rs;
-    a.bs = time_major ? 1 : p->T;
-    a.ts = time_major ? p->n_instances : 1;
+    fill_layout(a, time_major, p->n_instances, p->T);
     a.sigmacount = (long long *)d_sigmacount;
     MK_HIP(timing_start(ctx, 0));
     MK_HIP(dispatch_sparse((int)p->N, (int)p->K, a, ctx->stream));
@@ -716,21 +776,10 @@ static int do_filter(mk_context *ctx, const mk_problem *p, const mk_outputs *o)
     a.sym = (rec && (o->flags & MK_OUT_PACKED_SYM)) ? 1 : 0;
     // dense sigmas/detfs are [B,T] (stride 1); inside filtered records they are RS doubles apart
     a.sig_stride = (o->record_stride && !tape) ? o->record_stride : 1;
-    a.B = p->n_instances;
-    a.R = p->n_records;
-    a.T = p->T;
+    fill_model(a, p);
+    fill_initial(a, p);
+    fill_layout(a, (int)o->time_major, p->n_instances, p->T);
     a.warmup = p->warmup;
-    a.bs = o->time_major ? 1 : p->T;
-    a.ts = o->time_major ? p->n_instances : 1;
-    a.obs_bs = p->obs_time_major ? 1 : p->T;
-    a.obs_ts = p->obs_time_major ? p->n_records : 1;
-    a.obs = p->d_obs;
-    a.phi = p->d_phi;
-    a.q = p->d_q;
-    a.loadings = p->d_loadings;
-    a.obsvar = p->d_obsvar;
-    a.x0 = p->d_x0;
-    a.P0 = p->d_P0;
     a.mle = o->d_mle;
     a.sigmas = o->d_sigmas;
     a.detfs = o->d_detfs;
@@ -803,14 +852,12 @@ static int do_smooth(mk_context *ctx, const mk_problem *p, const mk_outputs *o, 
     }
     a.R = p->n_records;
     a.loadings = p->d_loadings;
-    a.scale = p->d_scale;
-    a.offset = p->d_offset;
+    fill_scaling(a, p);
     a.sim_means = o->d_sim_means;
     a.sim_vars = o->d_sim_vars;
     a.B = p->n_instances;
     a.T = p->T;
-    a.bs = o->time_major ? 1 : p->T;
-    a.ts = o->time_major ? p->n_instances : 1;
+    fill_layout(a, (int)o->time_major, p->n_instances, p->T);
     a.phi = p->d_phi;
     a.q = p->d_q;
     a.F = o->d_F;
@@ -962,23 +1009,33 @@ static mk::AdjointArgs adjoint_walk_args(const mk_problem *p, const double *d_wo
 {
     mk::AdjointArgs a;
     memset(&a, 0, sizeof(a));
-    a.B = p->n_instances;
-    a.R = p->n_records;
-    a.T = p->T;
-    a.bs = time_major ? 1 : p->T;
-    a.ts = time_major ? p->n_instances : 1;
+    fill_model(a, p);
+    fill_initial(a, p);
+    fill_layout(a, time_major, p->n_instances, p->T);
     a.rs = record_stride;
-    a.obs_bs = p->obs_time_major ? 1 : p->T;
-    a.obs_ts = p->obs_time_major ? p->n_records : 1;
-    a.obs = p->d_obs;
-    a.phi = p->d_phi;
-    a.q = p->d_q;
-    a.loadings = p->d_loadings;
-    a.obsvar = p->d_obsvar;
-    a.x0 = p->d_x0;
-    a.P0 = p->d_P0;
     a.F = d_work;
     return a;
+}
+
+// The recording forward pass every record reader starts with: filtered records only (+ the per-step bookkeeping in the record
+// pads) of record_stride doubles per (instance, step) at the head of d_work; with d_mle / d_sigmacount also the objective and the
+// step count (the gradient's forward phase).
+static int record_pass(mk_context *ctx, const mk_problem *p, double *d_work, int64_t record_stride, int time_major, uint32_t *d_status,
+                       double *d_mle = nullptr, int64_t *d_sigmacount = nullptr)
+{
+    const int64_t n = p->N + p->K;
+    mk_outputs o;
+    memset(&o, 0, sizeof(o));
+    o.d_mle = d_mle;
+    o.d_sigmacount = d_sigmacount;
+    o.d_status = d_status;
+    o.d_F = d_work;
+    o.d_Pf = d_work + n;
+    o.d_sigmas = d_work + n + n * n;
+    o.d_detfs = o.d_sigmas + 1;
+    o.time_major = time_major;
+    o.record_stride = record_stride;
+    return do_filter(ctx, p, &o);
 }
 
 MK_API int mk_loglik_grad(mk_context *ctx, const mk_problem *p, double *d_work, int time_major, double *d_mle,
@@ -997,37 +1054,25 @@ MK_API int mk_loglik_grad_phases(mk_context *ctx, const mk_problem *p, double *d
         return fail(MK_ERR_INVALID, "mk_loglik_grad_phases: phases must be MK_GRAD_FORWARD, MK_GRAD_BACKWARD or both");
     if (!d_work || !d_sigmacount || ((phases & MK_GRAD_FORWARD) && !d_mle) || ((phases & MK_GRAD_BACKWARD) && (!d_gphi || !d_gq)))
         return fail(MK_ERR_INVALID, "mk_loglik_grad: d_work and d_sigmacount are required; d_mle by the forward pass, d_gphi and d_gq by the backward pass");
-    const int64_t n = p->N + p->K;
     if (!specialised(p->N, p->K) || ctx->variant[MK_VARIANT_KERNEL_FAMILY] == 1)
         return fail(MK_ERR_SHAPE, "the adjoint gradient exists for specialised shapes (N + K <= 64: ahead-of-time list or a shape "
                                   "module); N=%lld, K=%lld runs the size-generic kernels, difference mk_loglik instead",
                     (long long)p->N, (long long)p->K);
-    // forward pass: filtered records only (+ per-step bookkeeping in the record pads), objective, step count
-    mk_outputs o;
-    memset(&o, 0, sizeof(o));
-    o.d_mle = d_mle;
-    o.d_sigmacount = d_sigmacount;
-    o.d_status = d_status;
-    o.d_F = d_work;
-    o.d_Pf = d_work + n;
-    o.d_sigmas = d_work + n + n * n;
-    o.d_detfs = o.d_sigmas + 1;
-    o.time_major = time_major;
-    o.record_stride = mk::record_stride((int)n);
+    const int64_t rs = mk::record_stride((int)(p->N + p->K));
     // wide models (16 < N + K): with an update tape on the context that holds this call (mk_set_adjoint_updates), the forward pass
     // records (d, 1/f, v) of every scalar update and the backward walk reads them instead of recomputing the step (round 6).
     // The decision depends on the tape, the shape and the sizes only: the two phases of one gradient agree.
     double *upd = nullptr;
     const int64_t us = mk_adjoint_update_stride(p->N, p->K);
     if (us > 0 && ctx->adj_upd && (size_t)(p->n_instances * p->T * us) <= ctx->adj_upd_cap) upd = ctx->adj_upd;
-    if (phases & MK_GRAD_FORWARD) {
+    if (phases & MK_GRAD_FORWARD) { // filtered records, objective, step count
         ctx->cur_upd = upd;
-        const int rc = do_filter(ctx, p, &o);
+        const int rc = record_pass(ctx, p, d_work, rs, time_major, d_status, d_mle, d_sigmacount);
         ctx->cur_upd = nullptr;
         if (rc) return rc;
     }
     if (!(phases & MK_GRAD_BACKWARD)) return MK_OK;
-    mk::AdjointArgs a = adjoint_walk_args(p, d_work, o.record_stride, time_major);
+    mk::AdjointArgs a = adjoint_walk_args(p, d_work, rs, time_major);
     a.upd = upd;
     a.us = upd ? us : 0;
     a.warmup = p->warmup;
@@ -1060,45 +1105,28 @@ MK_API int mk_loo(mk_context *ctx, const mk_problem *p, double *d_work, int time
         return fail(MK_ERR_SHAPE, "mk_loo serves specialised shapes with N + K <= 63 (ahead-of-time list or a shape module); "
                                   "N=%lld, K=%lld is not one%s", (long long)p->N, (long long)p->K,
                     ws ? " in this context (the size-generic kernel family is selected)" : "");
-    const int64_t n = p->N + p->K;
-    // the buffers' sizes: each must end inside the device allocation it starts in (an interior pointer of a pooled allocation
-    // passes whenever the pool's block is large enough -- the check catches a buffer that is too small, not every misuse)
-    const struct { const double *ptr; int64_t doubles; const char *name; } bufs[3] = {
-        {d_work, p->n_instances * p->T * ws, "d_work (n_instances * T * mk_loo_work_stride(N, K) doubles)"},
-        {d_loo_means, p->n_instances * p->T * p->N, "d_loo_means (n_instances * T * N doubles)"},
-        {d_loo_vars, p->n_instances * p->T * p->N, "d_loo_vars (n_instances * T * N doubles)"}};
-    for (const auto &b : bufs) {
-        hipDeviceptr_t base = nullptr;
-        size_t bytes = 0;
-        if (hipMemGetAddressRange(&base, &bytes, (hipDeviceptr_t)b.ptr) != hipSuccess) {
-            (void)hipGetLastError(); // not a hipMalloc allocation: its size cannot be known here
-            continue;
-        }
-        if ((const char *)b.ptr + b.doubles * (int64_t)sizeof(double) > (const char *)base + bytes)
-            return fail(MK_ERR_INVALID, "mk_loo: %s is larger than the device allocation it points into", b.name);
-    }
-    mk_outputs o;
-    memset(&o, 0, sizeof(o));
-    o.d_status = d_status;
-    o.d_F = d_work;
-    o.time_major = time_major;
-    o.record_stride = ws;
-    if (n <= 16) { // the recording forward pass of mk_loglik_grad, then the adjoint walk in its LOO mode
-        o.d_Pf = d_work + n;
-        o.d_sigmas = d_work + n + n * n;
-        o.d_detfs = o.d_sigmas + 1;
-        if (int rc = do_filter(ctx, p, &o)) return rc;
+    const device_buffer bufs[3] = {{d_work, p->n_instances * p->T * ws, "d_work (n_instances * T * mk_loo_work_stride(N, K) doubles)"},
+                                   {d_loo_means, p->n_instances * p->T * p->N, "d_loo_means (n_instances * T * N doubles)"},
+                                   {d_loo_vars, p->n_instances * p->T * p->N, "d_loo_vars (n_instances * T * N doubles)"}};
+    if (int rc = buffers_fit("mk_loo", bufs, 3)) return rc;
+    if (p->N + p->K <= 16) { // the recording forward pass, then the adjoint walk in its LOO mode
+        if (int rc = record_pass(ctx, p, d_work, ws, time_major, d_status)) return rc;
         mk::AdjointArgs a = adjoint_walk_args(p, d_work, ws, time_major);
         a.loo_means = d_loo_means;
         a.loo_vars = d_loo_vars;
-        a.scale = p->d_scale;
-        a.offset = p->d_offset;
+        fill_scaling(a, p);
         MK_HIP(timing_start(ctx, 1));
         MK_HIP(dispatch_loo((int)p->N, (int)p->K, &a, nullptr, ctx->stream));
         MK_HIP(timing_stop(ctx, 1));
         return MK_OK;
     }
     // wide models: the tape writer of the projection, then the tape walk in its LOO mode
+    mk_outputs o;
+    memset(&o, 0, sizeof(o));
+    o.d_status = d_status;
+    o.d_F = d_work;
+    o.time_major = time_major;
+    o.record_stride = ws;
     o.flags = MK_OUT_TAPE;
     o.d_sim_means = d_loo_means;
     o.d_sim_vars = d_loo_vars;
@@ -1110,14 +1138,12 @@ MK_API int mk_loo(mk_context *ctx, const mk_problem *p, double *d_work, int time
     a.rs = ws;
     a.R = p->n_records;
     a.loadings = p->d_loadings;
-    a.scale = p->d_scale;
-    a.offset = p->d_offset;
+    fill_scaling(a, p);
     a.sim_means = d_loo_means;
     a.sim_vars = d_loo_vars;
     a.B = p->n_instances;
     a.T = p->T;
-    a.bs = time_major ? 1 : p->T;
-    a.ts = time_major ? p->n_instances : 1;
+    fill_layout(a, time_major, p->n_instances, p->T);
     a.phi = p->d_phi;
     a.q = p->d_q;
     a.F = d_work;
@@ -1129,26 +1155,6 @@ MK_API int mk_loo(mk_context *ctx, const mk_problem *p, double *d_work, int time
 }
 
 // ---- simulation smoother (Durbin & Koopman 2002): the unconditional paths and the perturbed records (draw_kernels.hip) ----
-// Each buffer must end inside the device allocation it starts in (as in mk_loo: an interior pointer of a pooled allocation passes
-// whenever the pool's block is large enough -- the check catches a buffer that is too small, not every misuse).
-struct draw_buffer { const void *ptr; int64_t doubles; const char *name; };
-static int draw_buffers_fit(const char *who, const draw_buffer *bufs, int count)
-{
-    for (int k = 0; k < count; ++k) {
-        const draw_buffer &b = bufs[k];
-        if (!b.ptr) continue;
-        hipDeviceptr_t base = nullptr;
-        size_t bytes = 0;
-        if (hipMemGetAddressRange(&base, &bytes, (hipDeviceptr_t)b.ptr) != hipSuccess) {
-            (void)hipGetLastError(); // not a hipMalloc allocation: its size cannot be known here
-            continue;
-        }
-        if ((const char *)b.ptr + b.doubles * (int64_t)sizeof(double) > (const char *)base + bytes)
-            return fail(MK_ERR_INVALID, "%s: %s is larger than the device allocation it points into", who, b.name);
-    }
-    return MK_OK;
-}
-
 static int draw_counts(const char *who, int64_t first_instance, int64_t first_draw, int64_t ndraws)
 {
     if (ndraws < 1 || first_draw < 0 || first_instance < 0)
@@ -1170,32 +1176,22 @@ MK_API int mk_draw_perturb(mk_context *ctx, const mk_problem *p, uint64_t seed, 
     if (!p->d_obs || !p->d_loadings) return fail(MK_ERR_INVALID, "mk_draw_perturb: d_obs and d_loadings are required");
     if (!d_ystar) return fail(MK_ERR_INVALID, "mk_draw_perturb: d_ystar is required");
     const int64_t n = p->N + p->K, SB = ndraws * p->n_instances;
-    const draw_buffer bufs[4] = {{d_ystar, SB * p->T * p->N, "d_ystar (ndraws * n_instances * T * N doubles)"},
-                                 {d_zxplus, SB * p->T * p->N, "d_zxplus (ndraws * n_instances * T * N doubles)"},
-                                 {d_xplus, SB * p->T * n, "d_xplus (ndraws * n_instances * T * (N + K) doubles)"},
-                                 {d_L0, p->n_instances * n * n, "d_L0 (n_instances * (N + K)^2 doubles)"}};
-    if (int rc = draw_buffers_fit("mk_draw_perturb", bufs, 4)) return rc;
+    const device_buffer bufs[4] = {{d_ystar, SB * p->T * p->N, "d_ystar (ndraws * n_instances * T * N doubles)"},
+                                   {d_zxplus, SB * p->T * p->N, "d_zxplus (ndraws * n_instances * T * N doubles)"},
+                                   {d_xplus, SB * p->T * n, "d_xplus (ndraws * n_instances * T * (N + K) doubles)"},
+                                   {d_L0, p->n_instances * n * n, "d_L0 (n_instances * (N + K)^2 doubles)"}};
+    if (int rc = buffers_fit("mk_draw_perturb", bufs, 4)) return rc;
     mk::DrawArgs a;
     memset(&a, 0, sizeof(a));
-    a.B = p->n_instances;
-    a.R = p->n_records;
-    a.T = p->T;
+    fill_model(a, p);
+    fill_layout(a, (int)p->obs_time_major, SB, p->T); // the S * B paths follow the observations' layout
     a.N = (int)p->N;
     a.K = (int)p->K;
     a.S = ndraws;
-    a.bs = p->obs_time_major ? 1 : p->T;
-    a.ts = p->obs_time_major ? SB : 1;
-    a.obs_bs = p->obs_time_major ? 1 : p->T;
-    a.obs_ts = p->obs_time_major ? p->n_records : 1;
     a.seed = seed;
     a.first_instance = first_instance;
     a.first_draw = first_draw;
     a.antithetic = antithetic != 0;
-    a.obs = p->d_obs;
-    a.phi = p->d_phi;
-    a.q = p->d_q;
-    a.loadings = p->d_loadings;
-    a.obsvar = p->d_obsvar;
     a.L0 = d_L0;
     a.ystar = d_ystar;
     a.zxplus = d_zxplus;
@@ -1215,9 +1211,9 @@ MK_API int mk_draw_combine(mk_context *ctx, const mk_problem *p, int64_t ndraws,
         return fail(MK_ERR_INVALID, "mk_draw_combine: what must be MK_DRAW_SERIES or MK_DRAW_STATES (got %d)", what);
     if (!d_plus || !d_inout) return fail(MK_ERR_INVALID, "mk_draw_combine: d_plus and d_inout are required");
     const int64_t W = what == MK_DRAW_SERIES ? p->N : p->N + p->K, SB = ndraws * p->n_instances;
-    const draw_buffer bufs[2] = {{d_plus, SB * p->T * W, "d_plus (ndraws * n_instances * T * width doubles)"},
-                                 {d_inout, SB * p->T * W, "d_inout (ndraws * n_instances * T * width doubles)"}};
-    if (int rc = draw_buffers_fit("mk_draw_combine", bufs, 2)) return rc;
+    const device_buffer bufs[2] = {{d_plus, SB * p->T * W, "d_plus (ndraws * n_instances * T * width doubles)"},
+                                   {d_inout, SB * p->T * W, "d_inout (ndraws * n_instances * T * width doubles)"}};
+    if (int rc = buffers_fit("mk_draw_combine", bufs, 2)) return rc;
     mk::DrawCombineArgs a;
     memset(&a, 0, sizeof(a));
     a.SB = SB;
@@ -1241,8 +1237,8 @@ MK_API int mk_draw_normals(mk_context *ctx, uint64_t seed, int64_t first_instanc
     if (ninstances < 1 || T < 0 || ncomp < 1 || ncomp > 2 * MK_GENERIC_MAX_STATES)
         return fail(MK_ERR_INVALID, "mk_draw_normals: need ninstances >= 1, T >= 0 and 1 <= ncomp <= %d", 2 * MK_GENERIC_MAX_STATES);
     if (!d_out) return fail(MK_ERR_INVALID, "mk_draw_normals: d_out is required");
-    const draw_buffer buf = {d_out, ndraws * ninstances * (T + 1) * ncomp, "d_out (ndraws * ninstances * (T + 1) * ncomp doubles)"};
-    if (int rc = draw_buffers_fit("mk_draw_normals", &buf, 1)) return rc;
+    const device_buffer buf = {d_out, ndraws * ninstances * (T + 1) * ncomp, "d_out (ndraws * ninstances * (T + 1) * ncomp doubles)"};
+    if (int rc = buffers_fit("mk_draw_normals", &buf, 1)) return rc;
     mk::DrawNormalsArgs a;
     memset(&a, 0, sizeof(a));
     a.seed = seed;
@@ -1279,21 +1275,12 @@ MK_API int mk_disturbances(mk_context *ctx, const mk_problem *p, double *d_work,
                                   "N=%lld, K=%lld is not one%s", (long long)p->N, (long long)p->K,
                     ws ? " in this context (the size-generic kernel family is selected)" : "");
     const int64_t n = p->N + p->K;
-    const draw_buffer bufs[3] = {{d_work, p->n_instances * p->T * ws, "d_work (n_instances * T * mk_disturbance_work_stride(N, K) doubles)"},
-                                 {d_r, p->n_instances * p->T * n, "d_r (n_instances * T * (N + K) doubles)"},
-                                 {d_ninfo, p->n_instances * p->T * n, "d_ninfo (n_instances * T * (N + K) doubles)"}};
-    if (int rc = draw_buffers_fit("mk_disturbances", bufs, 3)) return rc;
-    // the recording forward pass of mk_loglik_grad (filtered records; no update tape: the walk recomputes), then the walk
-    mk_outputs o;
-    memset(&o, 0, sizeof(o));
-    o.d_status = d_status;
-    o.d_F = d_work;
-    o.d_Pf = d_work + n;
-    o.d_sigmas = d_work + n + n * n;
-    o.d_detfs = o.d_sigmas + 1;
-    o.time_major = time_major;
-    o.record_stride = ws;
-    if (int rc = do_filter(ctx, p, &o)) return rc;
+    const device_buffer bufs[3] = {{d_work, p->n_instances * p->T * ws, "d_work (n_instances * T * mk_disturbance_work_stride(N, K) doubles)"},
+                                   {d_r, p->n_instances * p->T * n, "d_r (n_instances * T * (N + K) doubles)"},
+                                   {d_ninfo, p->n_instances * p->T * n, "d_ninfo (n_instances * T * (N + K) doubles)"}};
+    if (int rc = buffers_fit("mk_disturbances", bufs, 3)) return rc;
+    // the recording forward pass (no update tape: the walk recomputes), then the walk
+    if (int rc = record_pass(ctx, p, d_work, ws, time_major, d_status)) return rc;
     mk::AdjointArgs a = adjoint_walk_args(p, d_work, ws, time_major);
     a.dist_r = d_r;
     a.dist_n = d_ninfo;
@@ -1320,48 +1307,24 @@ MK_API int mk_innovations(mk_context *ctx, const mk_problem *p, double *d_work, 
         return fail(MK_ERR_INVALID, "mk_innovations: nothing to write, give one of d_v, d_f, d_pred_means, d_pred_vars");
     if (!p->d_obs || !p->d_loadings) return fail(MK_ERR_INVALID, "d_obs and d_loadings are required");
     const int64_t ws = mk_innovations_work_stride(p->N, p->K);
-    if (!ws)
-        return fail(MK_ERR_SHAPE, "mk_innovations serves N + K <= %d states (got N=%lld, K=%lld)", mk::innov_max_states, (long long)p->N,
-                    (long long)p->K);
-    const int64_t n = p->N + p->K, cells = p->n_instances * p->T * p->N;
-    const draw_buffer bufs[5] = {{d_work, p->n_instances * p->T * ws, "d_work (n_instances * T * mk_innovations_work_stride(N, K) doubles)"},
-                                 {d_v, cells, "d_v (n_instances * T * N doubles)"},
-                                 {d_f, cells, "d_f (n_instances * T * N doubles)"},
-                                 {d_pred_means, cells, "d_pred_means (n_instances * T * N doubles)"},
-                                 {d_pred_vars, cells, "d_pred_vars (n_instances * T * N doubles)"}};
-    if (int rc = draw_buffers_fit("mk_innovations", bufs, 5)) return rc;
-    // the recording forward pass of mk_loglik_grad: filtered records only (+ the per-step bookkeeping in the record pads)
-    mk_outputs o;
-    memset(&o, 0, sizeof(o));
-    o.d_status = d_status;
-    o.d_F = d_work;
-    o.d_Pf = d_work + n;
-    o.d_sigmas = d_work + n + n * n;
-    o.d_detfs = o.d_sigmas + 1;
-    o.time_major = time_major;
-    o.record_stride = ws;
-    if (int rc = do_filter(ctx, p, &o)) return rc;
+    if (!ws) return too_many_states("mk_innovations", p, mk::innov_max_states);
+    const int64_t cells = p->n_instances * p->T * p->N;
+    const device_buffer bufs[5] = {{d_work, p->n_instances * p->T * ws, "d_work (n_instances * T * mk_innovations_work_stride(N, K) doubles)"},
+                                   {d_v, cells, "d_v (n_instances * T * N doubles)"},
+                                   {d_f, cells, "d_f (n_instances * T * N doubles)"},
+                                   {d_pred_means, cells, "d_pred_means (n_instances * T * N doubles)"},
+                                   {d_pred_vars, cells, "d_pred_vars (n_instances * T * N doubles)"}};
+    if (int rc = buffers_fit("mk_innovations", bufs, 5)) return rc;
+    if (int rc = record_pass(ctx, p, d_work, ws, time_major, d_status)) return rc;
     mk::InnovArgs a;
     memset(&a, 0, sizeof(a));
-    a.B = p->n_instances;
-    a.R = p->n_records;
-    a.T = p->T;
+    fill_model(a, p);
+    fill_initial(a, p);
+    fill_scaling(a, p);
+    fill_layout(a, time_major, p->n_instances, p->T);
     a.N = (int)p->N;
     a.K = (int)p->K;
-    a.bs = time_major ? 1 : p->T;
-    a.ts = time_major ? p->n_instances : 1;
     a.rs = ws;
-    a.obs_bs = p->obs_time_major ? 1 : p->T;
-    a.obs_ts = p->obs_time_major ? p->n_records : 1;
-    a.obs = p->d_obs;
-    a.phi = p->d_phi;
-    a.q = p->d_q;
-    a.loadings = p->d_loadings;
-    a.obsvar = p->d_obsvar;
-    a.x0 = p->d_x0;
-    a.P0 = p->d_P0;
-    a.scale = p->d_scale;
-    a.offset = p->d_offset;
     a.F = d_work;
     a.v = d_v;
     a.f = d_f;
@@ -1380,18 +1343,17 @@ MK_API int mk_innovation_stats(mk_context *ctx, int64_t B, int64_t T, int64_t N,
     if (B < 1 || T < 1 || N < 1 || t_first < 0 || nlags < 1 || nlags > mk::innov_max_lags)
         return fail(MK_ERR_INVALID, "mk_innovation_stats: need B, T, N >= 1, t_first >= 0 and 1 <= nlags <= %d", mk::innov_max_lags);
     if (!d_v || !d_f || !d_stats) return fail(MK_ERR_INVALID, "mk_innovation_stats: d_v, d_f and d_stats are required");
-    const draw_buffer bufs[3] = {{d_v, B * T * N, "d_v (B * T * N doubles)"},
-                                 {d_f, B * T * N, "d_f (B * T * N doubles)"},
-                                 {d_stats, B * N * (4 + nlags), "d_stats (B * N * (4 + nlags) doubles)"}};
-    if (int rc = draw_buffers_fit("mk_innovation_stats", bufs, 3)) return rc;
+    const device_buffer bufs[3] = {{d_v, B * T * N, "d_v (B * T * N doubles)"},
+                                   {d_f, B * T * N, "d_f (B * T * N doubles)"},
+                                   {d_stats, B * N * (4 + nlags), "d_stats (B * N * (4 + nlags) doubles)"}};
+    if (int rc = buffers_fit("mk_innovation_stats", bufs, 3)) return rc;
     mk::InnovStatsArgs a;
     memset(&a, 0, sizeof(a));
     a.B = B;
     a.T = T;
     a.N = (int)N;
     a.L = (int)nlags;
-    a.bs = time_major ? 1 : T;
-    a.ts = time_major ? B : 1;
+    fill_layout(a, time_major, B, T);
     a.t_first = t_first;
     a.v = d_v;
     a.f = d_f;
@@ -1413,9 +1375,8 @@ MK_API int mk_forecast(mk_context *ctx, const mk_problem *p, double *d_work, int
                        uint32_t *d_status)
 {
     MK_CTX(ctx);
-    if (p && p->N >= 1 && p->K >= 1 && p->N + p->K > mk::forecast_max_states)
-        return fail(MK_ERR_SHAPE, "mk_forecast serves N + K <= %d states (got N=%lld, K=%lld)", mk::forecast_max_states, (long long)p->N,
-                    (long long)p->K);
+    // refused first: every other shape that mk_forecast_work_stride does not serve is one check_problem refuses
+    if (p && p->N >= 1 && p->K >= 1 && p->N + p->K > mk::forecast_max_states) return too_many_states("mk_forecast", p, mk::forecast_max_states);
     if (int rc = check_problem(p)) return rc;
     if (!req) return fail(MK_ERR_INVALID, "mk_forecast: null mk_forecast_request");
     if (!d_work) return fail(MK_ERR_INVALID, "mk_forecast: d_work is required");
@@ -1432,18 +1393,15 @@ MK_API int mk_forecast(mk_context *ctx, const mk_problem *p, double *d_work, int
     if (!(req->coverage_z > 0.0) || !std::isfinite(req->coverage_z))
         return fail(MK_ERR_INVALID, "mk_forecast: coverage_z must be positive and finite");
     const int64_t ws = mk_forecast_work_stride(p->N, p->K);
-    if (!ws)
-        return fail(MK_ERR_SHAPE, "mk_forecast serves N + K <= %d states (got N=%lld, K=%lld)", mk::forecast_max_states, (long long)p->N,
-                    (long long)p->K);
-    const int64_t n = p->N + p->K, B = p->n_instances, rs = mk::record_stride((int)n);
-    const draw_buffer bufs[7] = {{d_work, B * p->T * ws, "d_work (n_instances * T * mk_forecast_work_stride(N, K) doubles)"},
-                                 {req->d_fan_origins, p->n_records, "d_fan_origins (n_records 64-bit integers)"},
-                                 {req->d_fan_means, B * req->horizon * p->N, "d_fan_means (n_instances * horizon * N doubles)"},
-                                 {req->d_fan_vars, B * req->horizon * p->N, "d_fan_vars (n_instances * horizon * N doubles)"},
-                                 {req->d_track_means, B * p->T * p->N, "d_track_means (n_instances * T * N doubles)"},
-                                 {req->d_track_vars, B * p->T * p->N, "d_track_vars (n_instances * T * N doubles)"},
-                                 {req->d_skill, B * p->N * req->horizon * 6, "d_skill (n_instances * N * horizon * 6 doubles)"}};
-    if (int rc = draw_buffers_fit("mk_forecast", bufs, 7)) return rc;
+    const int64_t B = p->n_instances, rs = mk::record_stride((int)(p->N + p->K));
+    const device_buffer bufs[7] = {{d_work, B * p->T * ws, "d_work (n_instances * T * mk_forecast_work_stride(N, K) doubles)"},
+                                   {req->d_fan_origins, p->n_records, "d_fan_origins (n_records 64-bit integers)"},
+                                   {req->d_fan_means, B * req->horizon * p->N, "d_fan_means (n_instances * horizon * N doubles)"},
+                                   {req->d_fan_vars, B * req->horizon * p->N, "d_fan_vars (n_instances * horizon * N doubles)"},
+                                   {req->d_track_means, B * p->T * p->N, "d_track_means (n_instances * T * N doubles)"},
+                                   {req->d_track_vars, B * p->T * p->N, "d_track_vars (n_instances * T * N doubles)"},
+                                   {req->d_skill, B * p->N * req->horizon * 6, "d_skill (n_instances * N * horizon * 6 doubles)"}};
+    if (int rc = buffers_fit("mk_forecast", bufs, 7)) return rc;
     if (fan && req->d_fan_origins) { // R integers to the host: an origin out of range would index outside the records
         std::vector<int64_t> h((size_t)p->n_records);
         MK_HIP(hipMemcpyAsync(h.data(), req->d_fan_origins, sizeof(int64_t) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
@@ -1453,43 +1411,21 @@ MK_API int mk_forecast(mk_context *ctx, const mk_problem *p, double *d_work, int
                 return fail(MK_ERR_INVALID, "mk_forecast: d_fan_origins[%lld] = %lld is outside -1 .. T - 1 = %lld", (long long)r,
                             (long long)h[(size_t)r], (long long)(p->T - 1));
     }
-    // the recording forward pass of mk_loglik_grad: filtered records only (+ the per-step bookkeeping in the record pads), packed
-    // at the head of d_work; the skill kernel's partial sums live behind them
-    mk_outputs o;
-    memset(&o, 0, sizeof(o));
-    o.d_status = d_status;
-    o.d_F = d_work;
-    o.d_Pf = d_work + n;
-    o.d_sigmas = d_work + n + n * n;
-    o.d_detfs = o.d_sigmas + 1;
-    o.time_major = time_major;
-    o.record_stride = rs;
-    if (int rc = do_filter(ctx, p, &o)) return rc;
+    // the records are packed at the head of d_work; the skill kernel's partial sums live behind them
+    if (int rc = record_pass(ctx, p, d_work, rs, time_major, d_status)) return rc;
     mk::ForecastArgs a;
     memset(&a, 0, sizeof(a));
-    a.B = B;
-    a.R = p->n_records;
-    a.T = p->T;
+    fill_model(a, p);
+    fill_initial(a, p);
+    fill_scaling(a, p);
+    fill_layout(a, time_major, B, p->T);
     a.N = (int)p->N;
     a.K = (int)p->K;
     a.H = (int)req->horizon;
     a.track_h = track ? req->track_horizon : 1;
     a.t_first = req->t_first;
-    a.bs = time_major ? 1 : p->T;
-    a.ts = time_major ? B : 1;
     a.rs = rs;
-    a.obs_bs = p->obs_time_major ? 1 : p->T;
-    a.obs_ts = p->obs_time_major ? p->n_records : 1;
     a.z2 = req->coverage_z * req->coverage_z;
-    a.obs = p->d_obs;
-    a.phi = p->d_phi;
-    a.q = p->d_q;
-    a.loadings = p->d_loadings;
-    a.obsvar = p->d_obsvar;
-    a.x0 = p->d_x0;
-    a.P0 = p->d_P0;
-    a.scale = p->d_scale;
-    a.offset = p->d_offset;
     a.F = d_work;
     a.fan_origins = req->d_fan_origins;
     a.fan_mean = req->d_fan_means;

@@ -706,26 +706,63 @@ class BatchedKalman:
         check(self._L.mk_filter_smooth(self._ctx, ctypes.byref(prob), ctypes.byref(o)))
         return res
 
+    # ------------------------------------------------------------------ the record readers: one scaffold
+    # loo_predict, disturbances, innovations and forecast run the recording forward pass into a workspace ("_work") and one kernel
+    # that reads its filtered records.  NOTE: loo_supported() and disturbances_supported() are methods, innovations_supported and
+    # forecast_supported properties -- an inconsistency of the public API that is kept.
+    def _reader_stride(self, fn, specialised_only, refusal=None):
+        """Doubles per (instance, step) of a record reader's workspace, the C ABI's ``fn(N, K)``; where the shape is not served
+        0, or with ``refusal`` (a text with places for N and K) a MetranHipError."""
+        served = self.loadings is not None and (not specialised_only or self.get_variant("kernel_family") == "specialised")
+        stride = int(fn(self.N, self.K)) if served else 0
+        if not stride and refusal is not None:
+            raise MetranHipError(refusal % (self.N, getattr(self, "K", None)))
+        return stride
+
+    def _bt_shapes(self, B, **tails):
+        """name -> (logical shape, follows the engine's layout) of ``[B,T,tail]`` buffers."""
+        return {key: ((B, self.T, tail), True) for key, tail in tails.items()}
+
+    def _reader_buffers(self, buffers, shapes, alloc, sep=","):
+        """The buffers of a record reader, ``shapes`` being name -> (logical shape, follows the engine's layout): allocated with a
+        zeroed ``status``, or the caller's ``buffers`` -- checked either way.  ``alloc`` names the allocator in the refusal."""
+        torch = _torch()
+        res = buffers
+        if res is None:
+            res = {key: self._empty_bt(*shape) if bt else torch.empty(shape, dtype=torch.float64, device=self.device)
+                   for key, (shape, bt) in shapes.items()}
+            res["status"] = torch.zeros(shapes["_work"][0][0], dtype=torch.int32, device=self.device)
+        for key, (shape, bt) in shapes.items():
+            t = res.get(key)
+            if t is None or tuple(t.shape) != shape or not ((self._layout(t) is t) if bt else t.is_contiguous()):
+                raise ValueError("buffers[%r] must be a [%s] tensor%s (%s)" % (key, sep.join("%d" % d for d in shape),
+                                                                              " in the engine's layout" if bt else "", alloc))
+        return res
+
+    @staticmethod
+    def _mask_bad_instances(res, keys):
+        """NaN in every row of the instances whose status carries ``FLAG_NONPOSITIVE_F``."""
+        bad = (res["status"] & FLAG_NONPOSITIVE_F) != 0
+        for key in keys:
+            res[key].masked_fill_(bad.view((-1,) + (1,) * (res[key].ndim - 1)), float("nan"))
+
     # ------------------------------------------------------------------ leave-one-out predictions
     def loo_supported(self):
         """True when ``loo_predict`` serves this engine's shape (C ABI ``mk_loo_work_stride`` > 0): specialised kernels and
         N + K <= 63 -- the adjoint walk over filtered records for N + K <= 16, the tape walk above."""
-        return (self.loadings is not None and self.get_variant("kernel_family") == "specialised"
-                and int(self._L.mk_loo_work_stride(self.N, self.K)) > 0)
+        return self._reader_stride(self._L.mk_loo_work_stride, True) > 0
 
     def _loo_stride(self):
-        if not self.loo_supported():
-            raise MetranHipError("leave-one-out predictions serve specialised shapes with N + K <= 63; (N=%s, K=%s) is not one"
-                                 % (self.N, getattr(self, "K", None)))
-        return int(self._L.mk_loo_work_stride(self.N, self.K))
+        return self._reader_stride(self._L.mk_loo_work_stride, True,
+                                   "leave-one-out predictions serve specialised shapes with N + K <= 63; (N=%s, K=%s) is not one")
+
+    def _loo_shapes(self, B):
+        return self._bt_shapes(B, _work=self._loo_stride(), loo_means=self.N, loo_vars=self.N)
 
     def alloc_loo(self, B):
         """Buffers of ``loo_predict`` for B instances (the forward pass's workspace + the two outputs), for callers that run
         it repeatedly (pass them back as ``buffers=``)."""
-        torch = _torch()
-        return {"_work": self._empty_bt(B, self.T, self._loo_stride()),
-                "loo_means": self._empty_bt(B, self.T, self.N), "loo_vars": self._empty_bt(B, self.T, self.N),
-                "status": torch.zeros(B, dtype=torch.int32, device=self.device)}
+        return self._reader_buffers(None, self._loo_shapes(B), "alloc_loo")
 
     def loo_predict(self, phi, q, x0=None, P0=None, buffers=None):
         """LEAVE-ONE-OUT predictions of every observed cell for B instances (C ABI ``mk_loo``): ``loo_means[b,t,j]`` is the
@@ -734,13 +771,9 @@ class BatchedKalman:
         cell gives (Metran's outlier screen, metran.py:464-506 + 831-883), parameters held fixed -- for all cells in two
         launches.  Units as set by ``set_scaling`` (scale / offset of the projection); NaN where a cell is not observed.
         Returns a dict with ``loo_means, loo_vars`` ``[B,T,N]`` and ``status`` (the filter's MK_FLAG_* bits)."""
-        stride = self._loo_stride()
+        self._loo_stride()
         prob, keep, B = self._problem(phi, q, 0, x0, P0)
-        res = buffers if buffers is not None else self.alloc_loo(B)
-        for key, tail in (("_work", stride), ("loo_means", self.N), ("loo_vars", self.N)):
-            t = res[key]
-            if tuple(t.shape) != (B, self.T, tail) or self._layout(t) is not t:
-                raise ValueError("buffers[%r] must be a [%d,%d,%d] tensor in the engine's layout (alloc_loo)" % (key, B, self.T, tail))
+        res = self._reader_buffers(buffers, self._loo_shapes(B), "alloc_loo")
         self._bind_stream()
         check(self._L.mk_loo(self._ctx, ctypes.byref(prob), self._p(res["_work"]), 1 if self.time_major else 0,
                              self._p(res["loo_means"]), self._p(res["loo_vars"]), self._p(res["status"])))
@@ -750,22 +783,19 @@ class BatchedKalman:
     def disturbances_supported(self):
         """True when ``disturbances`` serves this engine's shape (C ABI ``mk_disturbance_work_stride`` > 0): specialised
         kernels and N + K <= 64 -- ``adjoint_kernel`` for N + K <= 16, ``adjoint_wide_kernel`` above, in their disturbance mode."""
-        return (self.loadings is not None and self.get_variant("kernel_family") == "specialised"
-                and int(self._L.mk_disturbance_work_stride(self.N, self.K)) > 0)
+        return self._reader_stride(self._L.mk_disturbance_work_stride, True) > 0
 
     def _disturbance_stride(self):
-        if not self.disturbances_supported():
-            raise MetranHipError("state disturbances serve specialised shapes with N + K <= 64; (N=%s, K=%s) is not one"
-                                 % (self.N, getattr(self, "K", None)))
-        return int(self._L.mk_disturbance_work_stride(self.N, self.K))
+        return self._reader_stride(self._L.mk_disturbance_work_stride, True,
+                                   "state disturbances serve specialised shapes with N + K <= 64; (N=%s, K=%s) is not one")
+
+    def _disturbance_shapes(self, B):
+        return self._bt_shapes(B, _work=self._disturbance_stride(), r=self.n, ninfo=self.n)
 
     def alloc_disturbances(self, B):
         """Buffers of ``disturbances`` for B instances (the forward pass's workspace + the two outputs), for callers that run
         it repeatedly (pass them back as ``buffers=``)."""
-        torch = _torch()
-        return {"_work": self._empty_bt(B, self.T, self._disturbance_stride()),
-                "r": self._empty_bt(B, self.T, self.n), "ninfo": self._empty_bt(B, self.T, self.n),
-                "status": torch.zeros(B, dtype=torch.int32, device=self.device)}
+        return self._reader_buffers(None, self._disturbance_shapes(B), "alloc_disturbances")
 
     def disturbances(self, phi, q, x0=None, P0=None, buffers=None):
         """Smoothed STATE DISTURBANCES for B instances (C ABI ``mk_disturbances``): the Durbin-Koopman backward pair of the
@@ -775,14 +805,9 @@ class BatchedKalman:
         Koopman 1992; unit spread under the model, large where the state equation failed).  The raw pair is returned so that
         ``u`` is never formed from a difference.  Two launches: the recording forward pass and one backward walk.
         Returns a dict with ``r, ninfo`` ``[B,T,n]`` and ``status`` (the filter's MK_FLAG_* bits)."""
-        stride = self._disturbance_stride()
+        self._disturbance_stride()
         prob, keep, B = self._problem(phi, q, 0, x0, P0)
-        res = buffers if buffers is not None else self.alloc_disturbances(B)
-        for key, tail in (("_work", stride), ("r", self.n), ("ninfo", self.n)):
-            t = res[key]
-            if tuple(t.shape) != (B, self.T, tail) or self._layout(t) is not t:
-                raise ValueError("buffers[%r] must be a [%d,%d,%d] tensor in the engine's layout (alloc_disturbances)"
-                                 % (key, B, self.T, tail))
+        res = self._reader_buffers(buffers, self._disturbance_shapes(B), "alloc_disturbances")
         self._bind_stream()
         check(self._L.mk_disturbances(self._ctx, ctypes.byref(prob), self._p(res["_work"]), 1 if self.time_major else 0,
                                       self._p(res["r"]), self._p(res["ninfo"]), self._p(res["status"])))
@@ -795,22 +820,19 @@ class BatchedKalman:
     def innovations_supported(self):
         """True when ``innovations`` serves this engine's shape (C ABI ``mk_innovations_work_stride`` > 0): N + K <= 64,
         specialised or size-generic kernels alike."""
-        return self.loadings is not None and int(self._L.mk_innovations_work_stride(self.N, self.K)) > 0
+        return self._reader_stride(self._L.mk_innovations_work_stride, False) > 0
 
     def _innovations_stride(self):
-        if not self.innovations_supported:
-            raise MetranHipError("innovations serve shapes with N + K <= 64; (N=%s, K=%s) is not one" % (self.N, getattr(self, "K", None)))
-        return int(self._L.mk_innovations_work_stride(self.N, self.K))
+        return self._reader_stride(self._L.mk_innovations_work_stride, False,
+                                   "innovations serve shapes with N + K <= 64; (N=%s, K=%s) is not one")
+
+    def _innovations_shapes(self, B, outputs):
+        return self._bt_shapes(B, _work=self._innovations_stride(), **{key: self.N for key in outputs})
 
     def alloc_innovations(self, B, outputs=_INNOVATION_OUTPUTS):
         """Buffers of ``innovations`` for B instances (the forward pass's workspace + the outputs asked for), for callers that
         run it repeatedly (pass them back as ``buffers=``)."""
-        torch = _torch()
-        res = {"_work": self._empty_bt(B, self.T, self._innovations_stride()),
-               "status": torch.zeros(B, dtype=torch.int32, device=self.device)}
-        for key in outputs:
-            res[key] = self._empty_bt(B, self.T, self.N)
-        return res
+        return self._reader_buffers(None, self._innovations_shapes(B, outputs), "alloc_innovations")
 
     def innovations(self, phi, q, x0=None, P0=None, buffers=None, outputs=_INNOVATION_OUTPUTS):
         """ONE-STEP-AHEAD innovations for B instances (C ABI ``mk_innovations``): ``v[b,t,j]`` and ``f[b,t,j]`` are the innovation
@@ -823,21 +845,14 @@ class BatchedKalman:
         outputs = tuple(outputs)
         if not outputs or any(k not in self._INNOVATION_OUTPUTS for k in outputs):
             raise ValueError("outputs must be a non-empty subset of %s" % (self._INNOVATION_OUTPUTS,))
-        stride = self._innovations_stride()
+        self._innovations_stride()
         prob, keep, B = self._problem(phi, q, 0, x0, P0)
-        res = buffers if buffers is not None else self.alloc_innovations(B, outputs)
-        for key, tail in (("_work", stride),) + tuple((k, self.N) for k in outputs):
-            t = res.get(key)
-            if t is None or tuple(t.shape) != (B, self.T, tail) or self._layout(t) is not t:
-                raise ValueError("buffers[%r] must be a [%d,%d,%d] tensor in the engine's layout (alloc_innovations)"
-                                 % (key, B, self.T, tail))
+        res = self._reader_buffers(buffers, self._innovations_shapes(B, outputs), "alloc_innovations")
         ptr = {k: self._p(res[k]) if k in outputs else None for k in self._INNOVATION_OUTPUTS}
         self._bind_stream()
         check(self._L.mk_innovations(self._ctx, ctypes.byref(prob), self._p(res["_work"]), 1 if self.time_major else 0,
                                      ptr["v"], ptr["f"], ptr["pred_mean"], ptr["pred_var"], self._p(res["status"])))
-        bad = (res["status"] & FLAG_NONPOSITIVE_F) != 0
-        for k in outputs:
-            res[k].masked_fill_(bad[:, None, None], float("nan"))
+        self._mask_bad_instances(res, outputs)
         return res
 
     def innovation_stats(self, v, f, nlags=10, t_first=0):
@@ -872,16 +887,15 @@ class BatchedKalman:
     def forecast_supported(self):
         """True when ``forecast`` serves this engine's shape (C ABI ``mk_forecast_work_stride`` > 0): N + K <= 64,
         specialised or size-generic kernels alike."""
-        return self.loadings is not None and int(self._L.mk_forecast_work_stride(self.N, self.K)) > 0
+        return self._reader_stride(self._L.mk_forecast_work_stride, False) > 0
 
     def _forecast_stride(self):
-        if not self.forecast_supported:
-            raise MetranHipError("forecasts serve shapes with N + K <= 64; (N=%s, K=%s) is not one" % (self.N, getattr(self, "K", None)))
-        return int(self._L.mk_forecast_work_stride(self.N, self.K))
+        return self._reader_stride(self._L.mk_forecast_work_stride, False,
+                                   "forecasts serve shapes with N + K <= 64; (N=%s, K=%s) is not one")
 
     def _forecast_shapes(self, B, horizon, outputs):
         """name -> (logical shape, follows the engine's layout) of the buffers of ``forecast``."""
-        shapes = {"_work": ((B, self.T, self._forecast_stride()), True)}
+        shapes = self._bt_shapes(B, _work=self._forecast_stride())
         if "fan" in outputs:
             shapes["fan_mean"] = shapes["fan_var"] = ((B, horizon, self.N), False)
         if "track" in outputs:
@@ -902,12 +916,8 @@ class BatchedKalman:
     def alloc_forecast(self, B, horizon=14, outputs=("fan", "skill")):
         """Buffers of ``forecast`` for B instances (the forward pass's workspace + the outputs asked for), for callers that run
         it repeatedly (pass them back as ``buffers=``)."""
-        torch = _torch()
         horizon, outputs = self._forecast_request(horizon, outputs)
-        res = {"status": torch.zeros(B, dtype=torch.int32, device=self.device)}
-        for key, (shape, bt) in self._forecast_shapes(B, horizon, outputs).items():
-            res[key] = self._empty_bt(*shape) if bt else torch.empty(shape, dtype=torch.float64, device=self.device)
-        return res
+        return self._reader_buffers(None, self._forecast_shapes(B, horizon, outputs), "alloc_forecast", sep=", ")
 
     def forecast(self, phi, q, x0=None, P0=None, horizon=14, outputs=("fan", "skill"), origins=None, track_horizon=1, t_first=1,
                  coverage=0.95, buffers=None):
@@ -939,12 +949,8 @@ class BatchedKalman:
             raise ValueError("coverage must be in (0, 1)")
         self._forecast_stride()
         prob, keep, B = self._problem(phi, q, 0, x0, P0)
-        res = buffers if buffers is not None else self.alloc_forecast(B, horizon, outputs)
         shapes = self._forecast_shapes(B, horizon, outputs)
-        for key, (shape, bt) in shapes.items():
-            t = res.get(key)
-            if t is None or tuple(t.shape) != shape or not ((self._layout(t) is t) if bt else t.is_contiguous()):
-                raise ValueError("buffers[%r] must be a %s tensor%s (alloc_forecast)" % (key, list(shape), " in the engine's layout" if bt else ""))
+        res = self._reader_buffers(buffers, shapes, "alloc_forecast", sep=", ")
         org = None
         if origins is not None and "fan" in outputs:
             org = torch.as_tensor(origins, dtype=torch.int64).reshape(-1).to(self.device).contiguous()
@@ -960,10 +966,7 @@ class BatchedKalman:
         self._bind_stream()
         check(self._L.mk_forecast(self._ctx, ctypes.byref(prob), self._p(res["_work"]), 1 if self.time_major else 0, ctypes.byref(req),
                                   self._p(res["status"])))
-        bad = (res["status"] & FLAG_NONPOSITIVE_F) != 0
-        for key in shapes:
-            if key != "_work":
-                res[key].masked_fill_(bad.view((B,) + (1,) * (res[key].ndim - 1)), float("nan"))
+        self._mask_bad_instances(res, [key for key in shapes if key != "_work"])
         return res
 
     # ------------------------------------------------------------------ posterior draws (simulation smoother)
