@@ -517,6 +517,40 @@ MK_API int mk_draw_combine(mk_context *ctx, const mk_problem *prob, int64_t ndra
 MK_API int mk_draw_normals(mk_context *ctx, uint64_t seed, int64_t first_instance, int64_t ninstances, int64_t first_draw,
                            int64_t ndraws, int antithetic, int64_t T, int64_t ncomp, int raw, double *d_out);
 
+/* WINDOW STATISTICS of posterior draws, reduced on the device (ensemble_kernels.hip): what an ensemble of draws is read for --
+ * the uncertainty of a monthly mean, of a yearly minimum, of the time spent below a level -- without holding the ensemble.
+ *   mk_path_functionals reduces every path of a block of combined draws over time windows.  d_paths: logical
+ * [ndraws * n_instances, T, Wd], Wd = N (MK_DRAW_SERIES) or N + K (MK_DRAW_STATES), path id = s * n_instances + i as above, stored
+ * [T, ndraws * n_instances, Wd] when time_major is set.  d_windows int64 [n_records, W, 2]: window w of record r = i % n_records
+ * is the half-open step range [a, b).  PRECONDITION: 0 <= a_w <= b_w <= a_{w+1} <= ... <= T -- sorted, not overlapping; gaps and
+ * empty windows (a == b) are allowed.  The library does not read the windows on the host; for ANY input with 0 <= a <= b <= T the
+ * kernel stays inside its arrays (bounds outside that range are clamped into it), whatever the order -- the numbers are then
+ * those of the windows a forward walk meets.  d_thresholds [n_records, Wd] in the paths' units, or NULL.
+ *   d_functionals [ndraws, n_instances, Wd, W, 5] over y_t = path[t, j], t = a .. b - 1, L = b - a:
+ *     0 mean             (((y_a + y_{a+1}) + ...) + y_{b-1}) / L: the adds in increasing t, one division
+ *     1 min, 2 max       the smallest / largest y_t
+ *     3 fraction below   #{t : y_t < c} / L, c the threshold of (record, column)
+ *     4 longest spell    the largest number of consecutive steps with y_t < c, as a double; a spell ends at the window's edge
+ * An empty window gives NaN for all five, and so does a window that holds a NaN (a flagged path of draw_smoothed); a NaN or absent
+ * threshold makes 3 and 4 NaN.  The order of every sum is the definition's: the result does not depend on layout, batch or grid.
+ *   mk_ensemble_summary reduces d_values [S, cells] over the S draws of each cell, using the FINITE values x_s only, in
+ * increasing s: d_summary [cells, 5 + nprobs] = count m (as a double), mean (sequential sum / m; NaN if m = 0), sd (two-pass,
+ * sqrt(sum (x_s - mean)^2 / (m - 1)); NaN if m < 2), min, max (NaN if m = 0), then one quantile per probability p of the HOST array
+ * probs: with z the sorted finite values, h = (m - 1) p, lo = floor(h), q = z_lo + (h - lo) (z_min(lo+1, m-1) - z_lo) -- numpy's
+ * default "linear" quantile; NaN if m = 0.  Non-finite values are removed before the sort.  S <= mk_ensemble_max_draws() = 4096
+ * (the cell's values are sorted in LDS), S any number, nprobs <= 16.
+ *   Refusals (MK_ERR_INVALID, no launch, text in mk_last_error): W < 1, S < 1, S above the cap, cells < 1, nprobs < 0 or > 16, a
+ * probability outside [0, 1] or NaN, a missing pointer (d_thresholds may be NULL; probs may be NULL when nprobs = 0), `what`
+ * neither MK_DRAW_SERIES nor MK_DRAW_STATES, a buffer larger than the allocation it points into. */
+MK_API int64_t mk_path_functional_count(void); /* 5 */
+MK_API int mk_path_functionals(mk_context *ctx, const mk_problem *prob /* n_instances, n_records, T, N, K are read */, int64_t ndraws,
+                               int what /* MK_DRAW_SERIES or MK_DRAW_STATES */, int time_major, const double *d_paths, int64_t W,
+                               const int64_t *d_windows /* [n_records,W,2] */, const double *d_thresholds /* [n_records,Wd] or NULL */,
+                               double *d_functionals /* [ndraws,n_instances,Wd,W,5] */);
+MK_API int64_t mk_ensemble_max_draws(void);
+MK_API int mk_ensemble_summary(mk_context *ctx, int64_t S, int64_t cells, const double *d_values /* [S,cells] */, int64_t nprobs,
+                               const double *probs /* HOST array, nprobs <= 16 */, double *d_summary /* [cells, 5 + nprobs] */);
+
 /* kalmansmoother for B instances (kalmanfilter.py:403-476).  Reads out->d_F and out->d_Pf
  * (as written by mk_filter); predicted moments are recomputed from them (Phi diagonal), so
  * d_Xp/d_Pp are not read.  Writes d_S, d_Ps (either may be NULL), d_status.  d_status is OVERWRITTEN (cleared on the context's

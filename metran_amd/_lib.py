@@ -160,6 +160,10 @@ API = {
                                 c_void_p]),
     "mk_draw_combine": (c_int, [c_void_p, POINTER(Problem), c_int64, c_int, c_int, c_void_p, c_void_p]),
     "mk_draw_normals": (c_int, [c_void_p, c_uint64, c_int64, c_int64, c_int64, c_int64, c_int, c_int64, c_int64, c_int, c_void_p]),
+    "mk_path_functional_count": (c_int64, []),
+    "mk_path_functionals": (c_int, [c_void_p, POINTER(Problem), c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "mk_ensemble_max_draws": (c_int64, []),
+    "mk_ensemble_summary": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_dp, c_void_p]),
     "mk_standardize": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mk_mask_observations": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "mk_pack_observations": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),

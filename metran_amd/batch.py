@@ -13,6 +13,8 @@ number comes from the HIP kernels:
     disturbances             ->  smoothed state disturbances and auxiliary residuals (get_auxiliary_residuals, screen_breaks)
     forecast                 ->  multi-step-ahead forecasts and forecast skill by horizon (get_forecast, get_prediction_at,
                                  forecast_skill)
+    draw_smoothed            ->  posterior draws of series and states (get_simulation_draws, get_state_draws)
+    draw_window_statistics   ->  window statistics of the draws, reduced on the device (get_window_statistics)
 
 Results of the last filter / smoother run are cached per parameter set, like ``Metran._run_kalman`` does
 (metran.py:963-989): asking for another series, the variances after the means, or the decomposition after the
@@ -522,6 +524,60 @@ class MetranBatch:
         L = int(self.batch.lengths[r])
         return DataFrame(draws[:, r, :L, j].transpose(0, 1).cpu().numpy(), index=self.batch.index[r],
                          columns=["draw%d" % s for s in range(int(ndraws))])
+
+    # ------------------------------------------------------------------ window statistics of the draws
+    def _thresholds(self, thresholds):
+        """``thresholds`` of ``get_window_statistics`` as ``[R,N]`` in original units (NaN = no level), or None."""
+        if thresholds is None:
+            return None
+        if isinstance(thresholds, dict):
+            return np.array([[float(thresholds.get(name, np.nan)) for name in self.batch.names[r]] for r in range(self.R)])
+        thresholds = np.asarray(thresholds, dtype=np.float64)
+        if thresholds.ndim == 0:
+            return np.full((self.R, self.N), float(thresholds))
+        if thresholds.shape != (self.R, self.N):
+            raise ValueError("thresholds must be a scalar, a dict name -> level or an array [%d,%d]" % (self.R, self.N))
+        return thresholds
+
+    def get_window_statistics(self, windows, thresholds=None, ndraws=200, probs=(0.025, 0.5, 0.975), seed=0, alpha=None,
+                              antithetic=False):
+        """What the ensemble of ``get_simulation_draws`` is read for, without holding it: per model, series and time window the
+        posterior distribution of the window's ``mean``, ``min``, ``max``, ``fraction_below`` (the share of its steps below the
+        series' level) and ``longest_spell`` (the longest run of consecutive steps below it, in steps), summarised over
+        ``ndraws`` draws -- reduced on the device (``BatchedKalman.draw_window_statistics``), same draws as
+        ``get_simulation_draws(ndraws, seed)``, original units.  ``windows``: a pandas offset alias (``"MS"``, ``"YS"``, ``"W"``,
+        ...) or a list of ``(start, stop)`` timestamps, sorted and not overlapping; step t of a model is in a window when
+        ``start <= index[t] < stop`` on the model's own index (``metran_amd.windows.step_windows``).  ``thresholds``: a scalar, a
+        dict series name -> level, or an array ``[R,N]``; without a level the last two functionals are NaN.  Returns a DataFrame:
+        rows (model, series, window start), columns (functional, statistic) with the statistics ``count`` (draws used),
+        ``mean``, ``sd``, ``min``, ``max`` and one ``q<p>`` per probability; a window without a step of the model has count 0."""
+        from pandas import DataFrame, MultiIndex
+
+        from .kalmanfilter import check_status
+        from .windows import step_windows
+
+        steps, starts = step_windows(self.batch.index, windows, self.T)
+        probs = np.asarray(probs, dtype=np.float64).reshape(-1)
+        phi, q = self.kf.params_from_alpha(self._alpha(alpha), dt=self.dt)
+        self.kf.set_scaling(self._std, self._mean)
+        # a model's instance number is its place among ALL models, so its statistics do not depend on the number of ranks
+        out = self.kf.draw_window_statistics(phi, q, ndraws, steps, thresholds=self._thresholds(thresholds), probs=probs, seed=seed,
+                                             antithetic=antithetic, first_instance=self.shard[0])
+        check_status(out["status"].reshape(-1), "MetranBatch(window statistics)")
+        summary = out["summary"].cpu().numpy()   # [R,N,W,5,5+P]
+        functionals = ("mean", "min", "max", "fraction_below", "longest_spell")
+        statistics = ["count", "mean", "sd", "min", "max"] + ["q%g" % p for p in probs]
+        rows = [(r + self.shard[0], name, start) for r in range(self.R) for name in self.batch.names[r] for start in starts[r]]
+        values = [summary[r, :, : len(starts[r])].reshape(-1, len(functionals) * len(statistics)) for r in range(self.R)]
+        return DataFrame(np.concatenate(values, axis=0), index=MultiIndex.from_tuples(rows, names=["model", "series", "window"]),
+                         columns=MultiIndex.from_product([functionals, statistics], names=["functional", "statistic"]))
+
+    def get_window_statistic(self, r, name, windows, thresholds=None, ndraws=200, probs=(0.025, 0.5, 0.975), seed=0, alpha=None,
+                             antithetic=False):
+        """The rows of ``get_window_statistics`` for series ``name`` of model ``r``: DataFrame indexed by window start."""
+        self._series(r, name)
+        frame = self.get_window_statistics(windows, thresholds, ndraws, probs, seed, alpha, antithetic)
+        return frame.loc[(r + self.shard[0], name)]
 
     def _series(self, r, name):
         names = list(self.batch.names[r])

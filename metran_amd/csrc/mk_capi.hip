@@ -13,6 +13,7 @@
 #include <new>
 
 #include "draw_kernels.h"
+#include "ensemble_kernels.h"
 #include "forecast_kernels.h"
 #include "innov_kernels.h"
 #include "mk_generic.h"
@@ -1252,6 +1253,78 @@ MK_API int mk_draw_normals(mk_context *ctx, uint64_t seed, int64_t first_instanc
     a.raw = raw != 0;
     a.out = d_out;
     MK_HIP(mk::launch_draw_normals(a, ctx->stream));
+    return MK_OK;
+}
+
+// ---- window statistics of posterior draws (ensemble_kernels.hip) ----
+MK_API int64_t mk_path_functional_count(void) { return mk::path_functional_count; }
+
+MK_API int mk_path_functionals(mk_context *ctx, const mk_problem *p, int64_t ndraws, int what, int time_major, const double *d_paths,
+                               int64_t W, const int64_t *d_windows, const double *d_thresholds, double *d_functionals)
+{
+    MK_CTX(ctx);
+    if (!p) return fail(MK_ERR_INVALID, "null mk_problem");
+    if (p->n_instances <= 0 || p->n_records <= 0 || p->n_records > p->n_instances || p->T <= 0 || p->N <= 0 || p->K <= 0 || ndraws < 1)
+        return fail(MK_ERR_INVALID, "mk_path_functionals: need 1 <= n_records <= n_instances, T, N, K >= 1 and ndraws >= 1");
+    if (what != MK_DRAW_SERIES && what != MK_DRAW_STATES)
+        return fail(MK_ERR_INVALID, "mk_path_functionals: what must be MK_DRAW_SERIES or MK_DRAW_STATES (got %d)", what);
+    if (W < 1) return fail(MK_ERR_INVALID, "mk_path_functionals: need W >= 1 windows per record (got %lld)", (long long)W);
+    if (!d_paths || !d_windows || !d_functionals)
+        return fail(MK_ERR_INVALID, "mk_path_functionals: d_paths, d_windows and d_functionals are required");
+    const int64_t Wd = what == MK_DRAW_SERIES ? p->N : p->N + p->K, SB = ndraws * p->n_instances;
+    static_assert(sizeof(int64_t) == sizeof(double), "buffers_fit counts 8-byte words");
+    const device_buffer bufs[4] = {{d_paths, SB * p->T * Wd, "d_paths (ndraws * n_instances * T * width doubles)"},
+                                   {d_windows, p->n_records * W * 2, "d_windows (n_records * W * 2 int64)"},
+                                   {d_thresholds, p->n_records * Wd, "d_thresholds (n_records * width doubles)"},
+                                   {d_functionals, SB * Wd * W * mk::path_functional_count, "d_functionals (ndraws * n_instances * width * W * 5 doubles)"}};
+    if (int rc = buffers_fit("mk_path_functionals", bufs, 4)) return rc;
+    mk::PathFunctionalArgs a;
+    memset(&a, 0, sizeof(a));
+    a.SB = SB;
+    a.B = p->n_instances;
+    a.R = p->n_records;
+    a.T = p->T;
+    a.Wd = (int)Wd;
+    a.time_major = time_major != 0;
+    a.W = W;
+    a.paths = d_paths;
+    a.windows = d_windows;
+    a.thresholds = d_thresholds;
+    a.out = d_functionals;
+    MK_HIP(mk::launch_path_functionals(a, ctx->stream));
+    return MK_OK;
+}
+
+MK_API int64_t mk_ensemble_max_draws(void) { return mk::ensemble_max_draws; }
+
+MK_API int mk_ensemble_summary(mk_context *ctx, int64_t S, int64_t cells, const double *d_values, int64_t nprobs, const double *probs,
+                               double *d_summary)
+{
+    MK_CTX(ctx);
+    if (S < 1 || S > mk::ensemble_max_draws)
+        return fail(MK_ERR_INVALID, "mk_ensemble_summary: need 1 <= S <= mk_ensemble_max_draws() = %d draws (got %lld)", mk::ensemble_max_draws,
+                    (long long)S);
+    if (cells < 1) return fail(MK_ERR_INVALID, "mk_ensemble_summary: need cells >= 1 (got %lld)", (long long)cells);
+    if (nprobs < 0 || nprobs > mk::ensemble_max_probs)
+        return fail(MK_ERR_INVALID, "mk_ensemble_summary: need 0 <= nprobs <= %d (got %lld)", mk::ensemble_max_probs, (long long)nprobs);
+    if (!d_values || !d_summary || (nprobs > 0 && !probs))
+        return fail(MK_ERR_INVALID, "mk_ensemble_summary: d_values, d_summary and (with nprobs > 0) probs are required");
+    mk::EnsembleSummaryArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int64_t k = 0; k < nprobs; ++k) {
+        if (!(probs[k] >= 0.0 && probs[k] <= 1.0))
+            return fail(MK_ERR_INVALID, "mk_ensemble_summary: probs[%lld] = %g is not a probability in [0, 1]", (long long)k, probs[k]);
+        a.probs[k] = probs[k];
+    }
+    const device_buffer bufs[2] = {{d_values, S * cells, "d_values (S * cells doubles)"},
+                                   {d_summary, cells * (5 + nprobs), "d_summary (cells * (5 + nprobs) doubles)"}};
+    if (int rc = buffers_fit("mk_ensemble_summary", bufs, 2)) return rc;
+    a.S = S;
+    a.cells = cells;
+    a.nprobs = (int)nprobs;
+    a.values = d_values;
+    a.out = d_summary;
+    MK_HIP(mk::launch_ensemble_summary(a, ctx->stream));
     return MK_OK;
 }
 

@@ -1051,20 +1051,39 @@ class BatchedKalman:
         ensemble.  Returns ``{"draws": [S,B,T,N] or [S,B,T,n], "status": [S,B]}``; a path whose parameters are invalid (its
         simulated record is not finite at an observed cell) carries ``FLAG_NONPOSITIVE_F`` and NaN draws."""
         torch = _torch()
+        S = self._draw_check(ndraws, what, "draw_smoothed")
+        prob, keep, B = self._problem(phi, q, 1, x0, P0)
+        W = self.N if what == "series" else self.n
+        draws = torch.empty((S, B, self.T, W), dtype=torch.float64, device=self.device)
+        status = torch.empty((S, B), dtype=torch.int32, device=self.device)
+
+        def keep_chunk(s0, c, out, lost, flags):
+            draws[s0:s0 + c] = out.masked_fill(lost[:, None, None], float("nan")).unflatten(0, (c, B))
+            status[s0:s0 + c] = flags.view(c, B)
+
+        self._draw_chunks(prob, keep, B, S, what, seed, antithetic, first_draw, first_instance, chunk, keep_chunk)
+        return {"draws": draws, "status": status}
+
+    def _draw_check(self, ndraws, what, who):
         if what not in ("series", "states"):
             raise ValueError("what must be 'series' or 'states'")
         S = int(ndraws)
         if S < 1:
             raise ValueError("ndraws must be >= 1")
         if self.packed_sym:
-            raise MetranHipError("draw_smoothed needs a full-square engine (packed_sym=False)")
-        prob, keep, B = self._problem(phi, q, 1, x0, P0)
+            raise MetranHipError("%s needs a full-square engine (packed_sym=False)" % who)
+        return S
+
+    def _draw_chunks(self, prob, keep, B, S, what, seed, antithetic, first_draw, first_instance, chunk, sink):
+        """The chunk loop of the simulation smoother, shared by ``draw_smoothed`` and ``draw_window_statistics``: calls
+        ``sink(s0, c, out, lost, flags)`` per chunk of ``c`` draws starting at draw ``s0`` -- ``out`` the combined draws, logical
+        ``[c*B,T,W]`` in the engine's layout, which is the smoothing workspace (the sink reads it and keeps no reference),
+        ``lost [c*B]`` the flagged paths (``out`` is NOT masked for them) and ``flags [c*B]`` their status words.  The caller
+        allocates its results BEFORE the call: the chunk size comes from the memory that is free then."""
+        torch = _torch()
         phi_, q_, x0_, P0_ = keep
         L0 = torch.linalg.cholesky(P0_).contiguous() if P0_ is not None else None
         series = what == "series"
-        W = self.N if series else self.n
-        draws = torch.empty((S, B, self.T, W), dtype=torch.float64, device=self.device)
-        status = torch.empty((S, B), dtype=torch.int32, device=self.device)
         ws = getattr(self, "_draw_ws", None)
         if chunk is None:
             per = self._draw_bytes_per_draw(B, what)
@@ -1106,10 +1125,69 @@ class BatchedKalman:
             self._bind_stream()
             check(self._L.mk_draw_combine(self._ctx, ctypes.byref(prob), c, 0 if series else 1, 1 if self.time_major else 0,
                                           self._p(zx if series else xp), self._p(out)))
-            draws[s0:s0 + c] = out.masked_fill(lost[:, None, None], float("nan")).unflatten(0, (c, B))
-            status[s0:s0 + c] = (res["status"] | lost.to(torch.int32) * FLAG_NONPOSITIVE_F).view(c, B)
+            sink(s0, c, out, lost, res["status"] | lost.to(torch.int32) * FLAG_NONPOSITIVE_F)
             sub.obs = None   # y* of this chunk is done with
-        return {"draws": draws, "status": status}
+
+    def _step_windows(self, windows):
+        """``windows`` as the int64 ``[R,W,2]`` device tensor of ``mk_path_functionals``, its precondition checked here."""
+        torch = _torch()
+        w = windows.cpu().numpy() if isinstance(windows, torch.Tensor) else np.asarray(windows)
+        if w.ndim == 2:
+            w = np.broadcast_to(w, (self.R,) + w.shape)
+        if w.ndim != 3 or w.shape[0] != self.R or w.shape[1] < 1 or w.shape[2] != 2 or not np.issubdtype(w.dtype, np.integer):
+            raise ValueError("windows must be integer step ranges [R=%d,W>=1,2] (or [W,2] for all records)" % self.R)
+        w = np.ascontiguousarray(w, dtype=np.int64)
+        a, b = w[:, :, 0], w[:, :, 1]
+        if (a < 0).any() or (b > self.T).any() or (a > b).any():
+            raise ValueError("every window [a, b) needs 0 <= a <= b <= T = %d" % self.T)
+        if (b[:, :-1] > a[:, 1:]).any():
+            raise ValueError("the windows of a record must be sorted and must not overlap (b_w <= a_{w+1})")
+        return torch.from_numpy(w).to(self.device)
+
+    def draw_window_statistics(self, phi, q, ndraws, windows, thresholds=None, probs=(0.025, 0.5, 0.975), seed=0, what="series",
+                               x0=None, P0=None, antithetic=False, first_draw=0, first_instance=0, chunk=None,
+                               return_functionals=False):
+        """WINDOW STATISTICS of the posterior draws of ``draw_smoothed`` (same arguments, same draws), reduced on the device
+        inside its chunk loop: the ensemble ``[S,B,T,W]`` is never allocated.  ``windows`` int ``[R,W,2]`` (or ``[W,2]`` for all
+        records): half-open step ranges ``[a, b)`` per record, sorted and not overlapping, ``0 <= a <= b <= T`` (``ValueError``
+        otherwise); empty windows are allowed.  Per path, column and window ``mk_path_functionals`` takes the five functionals
+        mean, min, max, fraction of steps below ``thresholds [R,Wd]`` (the path's units; None or NaN: functionals 3, 4 are NaN)
+        and longest spell below it; over the draws of every cell one ``mk_ensemble_summary`` then takes count, mean, sd, min,
+        max and the quantiles ``probs`` (at most 16) of the finite values.  Returns ``{"summary": [B,Wd,W,5,5+P], "status":
+        [S,B]}`` and, with ``return_functionals``, ``"functionals": [S,B,Wd,W,5]``.  A flagged path (see ``draw_smoothed``) is NaN
+        in the functionals and therefore outside the summary's counts.  ``ndraws`` is at most ``mk_ensemble_max_draws()``."""
+        torch = _torch()
+        S = self._draw_check(ndraws, what, "draw_window_statistics")
+        cap, NF = int(self._L.mk_ensemble_max_draws()), int(self._L.mk_path_functional_count())
+        if S > cap:
+            raise ValueError("ndraws = %d is above the %d draws the ensemble summary serves" % (S, cap))
+        probs = np.ascontiguousarray(np.asarray(probs, dtype=np.float64).reshape(-1))
+        if probs.size > 16 or not ((probs >= 0.0) & (probs <= 1.0)).all():
+            raise ValueError("probs must be at most 16 probabilities in [0, 1]")
+        win = self._step_windows(windows)
+        prob, keep, B = self._problem(phi, q, 1, x0, P0)
+        Wd, W = (self.N if what == "series" else self.n), int(win.shape[1])
+        thr = self._dev(thresholds, (self.R, Wd), "thresholds") if thresholds is not None else None
+        functionals = torch.empty((S, B, Wd, W, NF), dtype=torch.float64, device=self.device)
+        summary = torch.empty((B, Wd, W, NF, 5 + probs.size), dtype=torch.float64, device=self.device)
+        status = torch.empty((S, B), dtype=torch.int32, device=self.device)
+
+        def reduce_chunk(s0, c, out, lost, flags):
+            part = functionals[s0:s0 + c]
+            self._bind_stream()
+            check(self._L.mk_path_functionals(self._ctx, ctypes.byref(prob), c, 0 if what == "series" else 1, 1 if self.time_major else 0,
+                                              self._p(out), W, self._p(win), self._p(thr), self._p(part)))
+            part.view(c * B, -1).masked_fill_(lost[:, None], float("nan"))
+            status[s0:s0 + c] = flags.view(c, B)
+
+        self._draw_chunks(prob, keep, B, S, what, seed, antithetic, first_draw, first_instance, chunk, reduce_chunk)
+        self._bind_stream()
+        check(self._L.mk_ensemble_summary(self._ctx, S, B * Wd * W * NF, self._p(functionals), probs.size,
+                                          probs.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), self._p(summary)))
+        res = {"summary": summary, "status": status}
+        if return_functionals:
+            res["functionals"] = functionals
+        return res
 
     def simulate_unconditional(self, phi, q, ndraws, seed=0, P0=None, antithetic=False, first_draw=0, first_instance=0):
         """Unconditional simulations of the model (the first half of ``draw_smoothed``, same kernel, same normals): ``xplus
