@@ -185,7 +185,7 @@ MK_API int mk_sync(mk_context *ctx);
  *                             2 the MFMA smoother without the fold
  *   MK_VARIANT_WIDE_FILTER    n > 16, N <= 32: 0 by batch size -- filter_split_kernel (series on the lanes, factor block
  *                             replicated: 2 or 4 models per wavefront) for more than 2 instances per SIMD of the device,
- *                             filter_kernel<N,K,64> (one state per lane) below; 1 the latter always; 2 the former always
+ *                             filter_wave_kernel<N,K> (one state per lane) below; 1 the latter always; 2 the former always
  *                             (the MK_OUT_TAPE path always runs the split kernel: the tape exists in that layout only)
  *   MK_VARIANT_SINGLE_RECORD  mk_filter with ONE record, at most MK_SPARSE_RECORD_MAX_INSTANCES instances, n <= 16 and both record
  *                             sets (the 7-tuple of seqkalmanfilter for a single Metran model): 0 the observed steps walked one

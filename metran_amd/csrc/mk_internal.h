@@ -56,10 +56,10 @@ struct FilterArgs {
     long long *sigmacount;
     double *F, *Pf, *Xp, *Pp;
     unsigned *status;
-    long variant;        // wide models: 0 = split layout when B > 2 x #SIMDs, else filter_kernel<N,K,64> (one state per lane); 1 = one state per lane always; 2 = split always
+    long variant;        // wide models: 0 = split layout (filter_split_kernel) when B > 2 x #SIMDs, else filter_wave_kernel (one state per lane); 1 = one state per lane always; 2 = split always
     long tape;           // 1: F is the backward tape of the inverse-free smoother (MK_OUT_TAPE; rs = tape_stride(N, K));
                          // 2: the STATE tape (MK_OUT_TAPE | MK_OUT_VAR_ONLY; rs = state_tape_stride(N, K))
-    double *upd;         // OUT = 3, one model per wavefront (16 < n): the UPDATE TAPE of the adjoint gradient (round 6), or NULL.  Per
+    double *upd;         // filter_wave_kernel OUT = 3 (16 < n): the UPDATE TAPE of the adjoint gradient (round 6), or NULL.  Per
     long us;             // (model, step) a block of us = adjoint_update_stride_c(N, K) doubles at (b*bs + t*ts)*us: slot u = the u-th scalar
                          // update of the step in ascending series order, [ d = P z_j' (n) | pad | 1/f, v ] -- what adjoint_wide_kernel
                          // otherwise recomputes from the filtered record of step t - 1

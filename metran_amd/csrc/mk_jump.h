@@ -56,18 +56,6 @@ __device__ __forceinline__ void pick16(double &dst, int j, double p0, double p1,
                    [p15] "v"(p15)
                  : "vcc", "scc");
 }
-// element j (wavefront-uniform, < N) of the lane's row, written to the lanes of MASK
-template <int N, int n, unsigned long long MASK>
-__device__ __forceinline__ void pick_column(double &dst, int j, const double (&P)[n])
-{
-#define MK_PE(i) P[(i) < N ? (i) : N - 1]
-    pick16<0, MASK>(dst, j, MK_PE(0), MK_PE(1), MK_PE(2), MK_PE(3), MK_PE(4), MK_PE(5), MK_PE(6), MK_PE(7), MK_PE(8), MK_PE(9),
-                    MK_PE(10), MK_PE(11), MK_PE(12), MK_PE(13), MK_PE(14), MK_PE(15));
-    if constexpr (N > 16)
-        pick16<16, MASK>(dst, j, MK_PE(16), MK_PE(17), MK_PE(18), MK_PE(19), MK_PE(20), MK_PE(21), MK_PE(22), MK_PE(23), MK_PE(24),
-                         MK_PE(25), MK_PE(26), MK_PE(27), MK_PE(28), MK_PE(29), MK_PE(30), MK_PE(31));
-#undef MK_PE
-}
 
 template <int CTRL>
 __device__ __forceinline__ double dpp_perm_f64(double v)

@@ -11,7 +11,7 @@
 // n^3 products of the smoother as 4x4x4 f64 MFMA blocks and measures slower.
 //
 // Reference semantics restated here (file:line in /root/reference):
-//   filter_kernel   : seqkalmanfilter  metran/kalmanfilter.py:236-400  + get_mle :550-567
+//   filter_kernel, filter_wave_kernel : seqkalmanfilter  metran/kalmanfilter.py:236-400  + get_mle :550-567
 //   smoother_kernel : kalmansmoother   metran/kalmanfilter.py:403-476
 //   simulate/decompose kernels : SPKalmanFilter.simulate/decompose :569-644
 //   params kernel   : Metran._phi / get_transition_* metran/metran.py:246-322
@@ -24,10 +24,12 @@ namespace mk {
 
 // =====================================================================================
 // Sequential-processing Kalman filter + -2 log L            (kalmanfilter.py:236-400, 550-567)
+//   two kernels: filter_kernel (n <= 16, a 16-lane group per model) and filter_wave_kernel (16 < n <= 64, one model per
+//   wavefront); launch_filter_nk picks by shape
 //   OUT  : 0 = no state outputs (solver objective, mk_loglik), 1 = predicted + filtered packed records,
 //          3 = filtered packed record only (input of a projecting smoother), 2 = any dense subset,
-//          4 = the BACKWARD TAPE of the inverse-free smoother (mk_dk.hip; G = 64 only: the shapes with more than 32 series,
-//              which the split layout of mk_split.hip -- the tape's writer for N <= 32 -- does not serve; same entries)
+//          4 = the BACKWARD TAPE of the inverse-free smoother (mk_dk.hip; filter_wave_kernel only: the shapes with more than 32
+//              series, which the split layout of mk_split.hip -- the tape's writer for N <= 32 -- does not serve; same entries)
 //   BOOK : per-step sigmas/detfs are written (needs one log per step); otherwise the
 //          log-determinant is accumulated as a normalised product with ONE log at the end
 // =====================================================================================
@@ -35,24 +37,13 @@ template <int n, int G, bool SYM>
 struct RecordIO;
 // packed records of the 16-lane kernels leave through wave-private LDS images as whole 16-byte chunks
 // (8 global_store_dwordx4 per step instead of 24 column-run dwordx2 stores: 1.52 -> 1.47 ms at B=4096)
-// resident wavefronts per SIMD asked of the compiler for the wide (one model per wavefront) filter
-#ifndef MK_WIDE_FILTER_WAVES
-#define MK_WIDE_FILTER_WAVES 2
-#endif
-// wide filter: scalar updates as a run-time loop over the observed series (1) or fully unrolled (0)
-#ifndef MK_WIDE_FILTER_LOOP
-#define MK_WIDE_FILTER_LOOP 1
-#endif
-#ifndef MK_FILTER_LDS_STORES
-#define MK_FILTER_LDS_STORES 1
-#endif
-// Deferred record emission of the 16-lane record filter (MK_FILTER_DEFER=0 builds the form that emits both records in one
-// block at the end of the step, for A/B runs).  With one wavefront per SIMD nothing else can issue while a wavefront waits,
-// and the end-of-step block was one wait after another: the per-step logarithm's dependent chain, the image's write -> read
-// round trip through LDS, then eight stores behind the reads' lgkmcnt waits -- from all four wavefronts of a CU at once.
+// Deferred record emission of the 16-lane record filter.  With one wavefront per SIMD nothing else can issue while a wavefront
+// waits, and an end-of-step emission block was one wait after another: the per-step logarithm's dependent chain, the image's
+// write -> read round trip through LDS, then eight stores behind the reads' lgkmcnt waits -- from all four wavefronts of a CU
+// at once.
 // The deferred schedule spreads the same instructions over the scalar updates (SLOT j = the point behind update j):
-//   predicted record : into imgP right after the prediction (as before);
-//   filtered record  : into imgF at the end of step t (as before); it leaves during step t + 1, the record of the last
+//   predicted record : into imgP right after the prediction;
+//   filtered record  : into imgF at the end of step t; it leaves during step t + 1, the record of the last
 //                      step after the loop;
 //   chunks           : the step's chunks (predicted and filtered alternating) are gathered ONE per slot from slot 0 on and
 //                      stored one slot behind their gather, so a store never waits for its LDS read, at most three chunks
@@ -65,16 +56,10 @@ struct RecordIO;
 //                      held its state across the updates and spilled; the f64 pipe is issue-bound, so the chain costs its
 //                      issue slots wherever it stands.)
 // Every multiply-add, its operands and its order are those of the undeferred form: the outputs are bit-identical.
-#ifndef MK_FILTER_DEFER
-#define MK_FILTER_DEFER 1
-#endif
-#ifndef MK_FILTER_DEFER_LOG
-#define MK_FILTER_DEFER_LOG 1
-#endif
 // ... the record kernels the schedule applies to are held to two resident wavefronts per SIMD (256 VGPRs; the 8192-model
 // flights run two), which they kept without being asked before -- up to 10 states and 16 hoisted loadings, where that holds
 // without scratch (compile-checked: (7,3) spills 40 bytes under it and is left to the allocator)
-#define MK_FILTER_WAVES(n, NK, G, OUT) ((MK_FILTER_DEFER && MK_FILTER_LDS_STORES && (G) == 16 && ((OUT) == 1 || (OUT) == 3) && (n) <= 10 && (NK) <= 16) ? 2 : 1)
+#define MK_FILTER_WAVES(n, NK, OUT) ((((OUT) == 1 || (OUT) == 3) && (n) <= 10 && (NK) <= 16) ? 2 : 1)
 // chunk q of a step's emission sequence is gathered at slot min(q, N - 1) and stored one slot later; slot N is the end of
 // the step, behind the put of the filtered image
 template <int N>
@@ -82,16 +67,15 @@ constexpr int filter_gather_slot(int q) { return q < N - 1 ? q : N - 1; }
 template <int N>
 constexpr int filter_store_slot(int q) { return filter_gather_slot<N>(q) + 1; }
 
-// (two resident wavefronts per SIMD are asked for only while the wide variant's two n-double row arrays fit
-// 256 VGPRs: compile-checked at n = 64, the constraint spilled 1.1 KB per lane)
+// ---- the 16-lane filter (n <= 16): four models per wavefront, one per DPP row; fully unrolled scalar updates ----
 template <int N, int K, int G, int OUT, bool BOOK, bool SYM>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 64 && N + K <= 40 ? MK_WIDE_FILTER_WAVES : MK_FILTER_WAVES(N + K, N * K, G, OUT)))) filter_kernel(FilterArgs a)
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MK_FILTER_WAVES(N + K, N * K, OUT)))) filter_kernel(FilterArgs a)
 {
+    static_assert(G == 16, "a 16-lane group per model; wider models are filter_wave_kernel's");
+    static_assert(OUT == 0 || OUT == 1 || OUT == 2 || OUT == 3, "the tape leaves the one-model-per-wavefront filter");
     static_assert(!SYM || OUT == 1 || OUT == 3, "packed-symmetric layout applies to record outputs");
     constexpr int n = N + K;
     static_assert(n <= G, "state dimension must fit the lane group");
-    constexpr bool TAPE = (OUT == 4);
-    static_assert(!TAPE || (G == 64 && MK_WIDE_FILTER_LOOP && N * K > 32), "the tape leaves the one-model-per-wavefront loop filter");
     using Gp = Group<G>;
     constexpr int GPB = 256 / G; // models per 256-thread workgroup
     constexpr bool HOIST = (N * K <= 32); // keep Z's loading block replicated in registers
@@ -107,42 +91,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 6
     // per-model constants: lane r holds phi_r, q_r; lane j < N holds loadings[j,:] and obsvar[j]
     const double phi_r = a.phi[inst * n + r];
     const double q_r = a.q[inst * n + r];
-    // row r of Phi (x) Phi and of Q = diag(q) in registers -- except for one model per wavefront
-    // (n > 16), where those 4n VGPRs are what stands between one and two resident wavefronts per SIMD:
-    // there diag(Phi) is read back from LDS every step (wavefront-uniform address) and Q's row is re-selected
-    constexpr bool WIDE = (G == 64);
-    double pp[WIDE ? 1 : n], qd[WIDE ? 1 : n];
-    constexpr int NP = n + (n & 1); // even: rows of 16-byte pieces
-    __shared__ __attribute__((aligned(16))) double lds_phi[WIDE ? (256 / G) * 3 * NP : 1];
-    double *phim = lds_phi + (WIDE ? (threadIdx.x / G) * 3 * NP : 0); // diag(Phi)
-    double *dvec = phim + (WIDE ? NP : 0);                             // d = P Z_j^T of the current update
-    double *dvec2 = dvec;                                              // (loop filter: two buffers, alternating)
-    if constexpr (WIDE) {
-        phim[r] = phi_r;
-        wave_lds_sync();
-    } else {
-        sfor<0, n>(MK_LAMBDA(c) {
-            pp[decltype(c)::value] = phi_r * Gp::template bcast<decltype(c)::value>(phi_r);
-            qd[decltype(c)::value] = (decltype(c)::value == r) ? q_r : 0.0;
-        });
-    }
+    // row r of Phi (x) Phi and of Q = diag(q) in registers
+    double pp[n], qd[n];
+    sfor<0, n>(MK_LAMBDA(c) {
+        pp[decltype(c)::value] = phi_r * Gp::template bcast<decltype(c)::value>(phi_r);
+        qd[decltype(c)::value] = (decltype(c)::value == r) ? q_r : 0.0;
+    });
     const int jr = lane < N ? lane : N - 1;
     double gam[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) gam[k] = a.loadings[(rec * N + jr) * K + k];
     const double rvar = a.obsvar ? a.obsvar[rec * N + jr] : 0.0;
-    // WIDE and too many loadings to replicate in registers: a wave-private LDS copy read at wavefront-uniform
-    // addresses (two 16-byte reads per update for K = 4) instead of 2 K v_readlane per update
-    constexpr bool GTAB = WIDE && !HOIST;
-    __shared__ __attribute__((aligned(16))) double lds_gam[GTAB ? (256 / G) * N * K : 1];
-    double *gtab = lds_gam + (GTAB ? (threadIdx.x / G) * N * K : 0);
-    if constexpr (GTAB) {
-        if (lane < N) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) gtab[lane * K + k] = gam[k];
-        }
-        wave_lds_sync();
-    }
     double Gh[HOIST ? N : 1][K]; // Gh[j][k] = loadings[j,k] in every lane
     if constexpr (HOIST) {
         sfor<0, N>(MK_LAMBDA(j) {
@@ -158,65 +117,44 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 6
 #pragma unroll
     for (int c = 0; c < n; ++c) P[c] = a.P0 ? a.P0[(inst * n + r) * n + c] : (c == r ? 1.0 : 0.0);
 
-    // wide loop filter: the K common-factor states (and their phi) replicated in every lane, updated with the gain
-    // elements broadcast at the END of an update (next to the rank-one update) -- the innovation of the next update
-    // then starts from registers instead of K dependent readlane pairs at the head of its chain
-    constexpr bool XREP = WIDE && MK_WIDE_FILTER_LOOP;
-    double xk[XREP ? K : 1], phik[XREP ? K : 1];
-    if constexpr (XREP) {
-        sfor<0, K>(MK_LAMBDA(k) {
-            xk[decltype(k)::value] = Gp::template bcast<N + decltype(k)::value>(x);
-            phik[decltype(k)::value] = Gp::template bcast<N + decltype(k)::value>(phi_r);
-        });
-    }
-
     // outputs: (b, t) lives at block index b*bs + t*ts -- (T, 1) model-major or (1, B) time-major
     constexpr bool RECF = (OUT == 1 || OUT == 3); // filtered moments go to packed records
-    MomentPtr oP = moment_ptr<n>(a.Xp, a.Pp, inst * a.bs, a.ts, OUT == 1 ? a.rs : 0, r); // predicted moments
-    MomentPtr oF = moment_ptr<n>(a.F, a.Pf, inst * a.bs, a.ts, RECF ? a.rs : 0, r);      // filtered moments
-    // OUT == 1 (packed records): the RS - NV pad doubles of both records are written too (whole cache
-    // lines): lane l owns pad slot min(l, PADN-1); filtered record: slot 0 = sigma, slot 1 = detf, rest 0
-    // (RS / NVO: stride and payload of the record in HBM -- full-square or packed-symmetric)
+    MomentPtr oP = moment_ptr<n>(a.Xp, a.Pp, inst * a.bs, a.ts, 0, r); // predicted moments (OUT == 2)
+    MomentPtr oF = moment_ptr<n>(a.F, a.Pf, inst * a.bs, a.ts, 0, r);  // filtered moments (OUT == 2)
+    // packed records: the RS - NVO pad doubles of both records are written too (whole cache lines); filtered record:
+    // slot 0 = sigma, slot 1 = detf, rest 0  (RS / NVO: stride and payload of the record in HBM -- full-square or packed-symmetric)
     constexpr int RS = SYM ? record_stride_sym_c(n) : record_stride_c(n), NVO = SYM ? record_payload_sym(n) : NV;
-    constexpr int PADN = RS - NVO;
-    const int pslot = lane < PADN ? lane : PADN - 1;
-    double *padF = RECF ? a.F + inst * a.bs * RS + NVO + pslot : nullptr;
-    double *padP = OUT == 1 ? a.Xp + inst * a.bs * RS + NVO + pslot : nullptr;
-    // records leave through wave-private LDS images as whole 16-byte chunks (as in the smoother)
-    constexpr bool LDSOUT = MK_FILTER_LDS_STORES && RECF && G == 16;
+    // records leave through wave-private LDS images as whole 16-byte chunks (as in the smoother), on the deferred schedule
+    // (see the top of the file)
     using RIO = RecordIO<n, G, SYM>;
-    __shared__ __attribute__((aligned(16))) double lds_rec[LDSOUT ? 4 * 2 * RIO::LDS_PER_WAVE : 1];
-    double *imgP = lds_rec + (LDSOUT ? (threadIdx.x / 64) * 2 * RIO::LDS_PER_WAVE : 0);
-    double *imgF = imgP + (LDSOUT ? RIO::LDS_PER_WAVE : 0);
+    __shared__ __attribute__((aligned(16))) double lds_rec[RECF ? 4 * 2 * RIO::LDS_PER_WAVE : 1];
+    double *imgP = lds_rec + (RECF ? (threadIdx.x / 64) * 2 * RIO::LDS_PER_WAVE : 0);
+    double *imgF = imgP + (RECF ? RIO::LDS_PER_WAVE : 0);
     const int lane64 = threadIdx.x & 63, gw = lane64 / G;
     typename RIO::Map rmap;
     double *recP = a.Xp, *recF = a.F;
     const long rstep = a.ts * RS;
-    if constexpr (LDSOUT) {
+    if constexpr (RECF) {
         rmap = RIO::make_map(lane64, (long)blockIdx.x * GPB + (threadIdx.x / 64) * RIO::GW, a.B, a.bs);
         RIO::clear_tail(imgP, lane64);
         RIO::clear_tail(imgF, lane64);
         RIO::put_pad(imgP, gw, 0.0, 0.0);
-        if constexpr (MK_FILTER_DEFER) {
-            RIO::put(imgF, gw, r, x, P); // what step 0 finds in the carried record's image
-            RIO::put_pad(imgF, gw, 0.0, 0.0);
-        }
+        RIO::put(imgF, gw, r, x, P); // what step 0 finds in the carried record's image
+        RIO::put_pad(imgF, gw, 0.0, 0.0);
     }
     double pad0 = 0.0, pad1 = 0.0;
     double sum_sig = 0.0, sum_det = 0.0;
     long sc = 0; // compressed index of the next observed step
-    // ---- deferred emission (MK_FILTER_DEFER, see the top of the file) ----
-    constexpr bool FDEFER = MK_FILTER_DEFER && LDSOUT;
     // the packed-symmetric two-record kernel holds eight more map registers: with the carried logarithm it spills at n = 10,
-    // so there detf is formed at the end of its own step as before (and the step's last chunk store is issued before it)
-    constexpr bool FDLOG = FDEFER && BOOK && MK_FILTER_DEFER_LOG && !(SYM && OUT == 1);
+    // so there detf is formed at the end of its own step (and the step's last chunk store is issued before it)
+    constexpr bool FDLOG = RECF && BOOK && !(SYM && OUT == 1);
     constexpr int FPER = RIO::PER;
     constexpr int FNC = (OUT == 1 ? 2 : 1) * FPER; // chunks a lane moves per step; OUT == 1: P0 F0 P1 F1 ...
     double c_sigma = 0.0, c_fmant = 1.0; // sigma and the normalised product of the f's of the carried step
     int c_fexp = 0;                      // ... and the product's exponent
     bool c_has = false;                  // it observed something (then its compressed index is sc - 1)
     typename RIO::chunk_t ch[FNC];
-    // where the carried filtered record goes.  Step 0 has none: it stores the initial moments (put below) to record 0, where
+    // where the carried filtered record goes.  Step 0 has none: it stores the initial moments (put above) to record 0, where
     // the same lanes store the filtered record of step 0 one step later -- a branch around the stores of step 0 costs 14
     // VGPRs in every step (the chunks then live across control flow), which the kernel does not have
     double *recFc = a.F;
@@ -252,7 +190,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 6
         }
     };
     auto slot = MK_LAMBDA(jc) { // behind update j (fixed series indices: also where the update itself is masked out)
-        if constexpr (FDEFER) {
+        if constexpr (RECF) {
             constexpr int j = decltype(jc)::value;
             sfor<0, FNC>(MK_LAMBDA(qc) { // the chunks gathered at the slot before
                 if constexpr (filter_store_slot<N>(decltype(qc)::value) == j) chunk_store(qc);
@@ -268,11 +206,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 6
             __builtin_amdgcn_sched_barrier(0); // the stores stay one update apart
         }
     };
-    // TAPE: block of (model, step) = N (state tape: N + K) entries [ vector in the observable basis (n) | s0 s1 s2 0 ] of
-    // XS = n + 4 doubles (mk_internal.h); lane r < n holds element r of an entry's vector
-    [[maybe_unused]] constexpr int XS = tape_xs_c(N, K);
-    [[maybe_unused]] double *trec = TAPE ? a.F + inst * a.bs * a.rs : nullptr;
-    [[maybe_unused]] const long tstep = a.ts * a.rs;
 
     // ---- observation stream: tiles of 16 time steps through LDS ----
     // vmcnt retires vector-memory operations IN ORDER, so consuming a load makes the wavefront wait for
@@ -288,7 +221,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 6
     // steps before parking it from inside a single loop: the phi copies of the staging registers on the
     // 14 other steps each came with an `s_waitcnt vmcnt(0)` -- a full drain of the store queue EVERY step,
     // 23 % of the filter's cycles in SQ_WAIT_INST_ANY.)
-    const int lrow = lane < TS ? lane : TS - 1; // lanes >= TS (G = 64) duplicate row TS-1
+    const int lrow = lane; // G == TS: one row per lane
+    static_assert(G == TS, "lane l stages row l of the tile");
     constexpr bool OV2 = (N % 2 == 0);          // 16-byte row pieces when rows are 16-byte aligned
     constexpr int ONC = OV2 ? N / 2 : N;
     using ochunk_t = typename std::conditional<OV2, v2d, double>::type;
@@ -296,32 +230,19 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 6
     double *otile = lds_obs + (threadIdx.x / G) * TS * N; // this model's tile
     const double *obase = a.obs + rec * a.obs_bs * N;
     const long ostep = a.obs_ts * N;
-    ochunk_t oreg[WIDE ? 1 : ONC];
-    // WIDE (one model per wavefront): a step takes ~10 us, the once-per-tile wait for the store queue is
-    // noise, and the N staging registers held across two steps are not: fetch and park in one go
-    long otr = 0;
+    ochunk_t oreg[ONC];
     auto obs_issue = [&](long t0) __attribute__((always_inline)) { // HBM -> registers, row min(t0+lane, T-1)
         long tr = t0 + lrow;
         if (tr > T - 1) tr = T - 1;
-        if constexpr (WIDE) {
-            otr = tr;
-        } else {
-            const ochunk_t *src = reinterpret_cast<const ochunk_t *>(obase + tr * ostep);
+        const ochunk_t *src = reinterpret_cast<const ochunk_t *>(obase + tr * ostep);
 #pragma unroll
-            for (int i = 0; i < ONC; ++i) oreg[i] = src[i];
-        }
+        for (int i = 0; i < ONC; ++i) oreg[i] = src[i];
     };
     auto obs_park = [&]() __attribute__((always_inline)) { // registers -> the LDS tile
         ochunk_t *dst = reinterpret_cast<ochunk_t *>(otile + lrow * N);
         wave_lds_sync(); // the previous tile's reads are complete
-        if constexpr (WIDE) {
-            const ochunk_t *src = reinterpret_cast<const ochunk_t *>(obase + otr * ostep);
 #pragma unroll
-            for (int i = 0; i < ONC; ++i) dst[i] = src[i];
-        } else {
-#pragma unroll
-            for (int i = 0; i < ONC; ++i) dst[i] = oreg[i];
-        }
+        for (int i = 0; i < ONC; ++i) dst[i] = oreg[i];
         wave_lds_sync();
     };
     obs_issue(0);
@@ -351,31 +272,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 6
 
         // ---- predict (:318-331; Phi diagonal) ----
         x = phi_r * x;
-        if constexpr (XREP) {
 #pragma unroll
-            for (int k = 0; k < K; ++k) xk[k] = phik[k] * xk[k];
-        }
-        if constexpr (WIDE) {
-            int rv = r; // opaque copies: keeps the n selects inside the loop (hoisted, they are 2n VGPRs)
-            double qv = q_r;
-            asm volatile("" : "+v"(rv), "+v"(qv));
-            double phc[n];
-            load_row<n>(phim, phc);
-#pragma unroll
-            for (int c = 0; c < n; ++c) P[c] = fma(P[c] * phi_r, phc[c], c == rv ? qv : 0.0);
-        } else {
-#pragma unroll
-            for (int c = 0; c < n; ++c) P[c] = fma(P[c], pp[c], qd[c]);
-        }
-        if constexpr (LDSOUT && OUT == 1) {
-            RIO::put(imgP, gw, r, x, P);
-        } else if constexpr (OUT == 1) {
-            *oP.vec = x;               // :332
-            if constexpr (SYM) store_cols_sym<n>(oP.mat - r, P, r);
-            else store_cols<n>(oP.mat, P);  // :333
-            *padP = 0.0;
-            oP.advance_nn(1);
-            padP += a.ts * RS;
+        for (int c = 0; c < n; ++c) P[c] = fma(P[c], pp[c], qd[c]);
+        if constexpr (OUT == 1) {
+            RIO::put(imgP, gw, r, x, P); // :332-333
         } else if constexpr (OUT == 2) {
             if (oP.vec) *oP.vec = x;
             if (oP.mat) store_cols<n>(oP.mat, P);
@@ -402,13 +302,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 6
                 constexpr int kk = decltype(k)::value;
                 double g;
                 if constexpr (HOIST) g = Gh[j][kk];
-                else if constexpr (GTAB) g = gtab[j * K + kk];
                 else g = Gp::template bcast<j>(gam[kk]);
                 dr = fma(P[N + kk], g, dr);
             });
             // innovation variance f = R_j + Z_j d (:359-362), formed at lane j from d_j, d_{N+k}
             double fl = rvar + dr;
-            if constexpr (G == 16) dpp_pin(dr);
+            dpp_pin(dr);
             sfor<0, K>(MK_LAMBDA(k) {
                 constexpr int kk = decltype(k)::value;
                 Gp::template fmac<N + kk, false>(fl, dr, gam[kk]); // fl += d_{N+k} * gam_k
@@ -417,19 +316,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 6
             const double rf = rcp_nr(f);
             const double kr = dr * rf; // Kalman gain element r (:364-366)
             // P -= k k^T f (:368-372): P[r][c] -= d_c * k_r, d_c broadcast from lane c
-            if constexpr (WIDE) {
-                // n broadcasts through readlane are 2n VALU + n FMA issues; through LDS (every lane stores
-                // its d_r, then reads the whole vector at a wavefront-uniform address) the VALU sees only
-                // the n FMAs -- these kernels are VALU-issue bound (one f64 wave instruction per 4 cycles)
-                dvec[r] = dr;
-                wave_lds_sync();
-                double dc[n];
-                load_row<n>(dvec, dc);
-#pragma unroll
-                for (int c = 0; c < n; ++c) P[c] = fma(-dc[c], kr, P[c]);
-            } else {
-                Gp::template axpy_col<0, n, true, n>(P, dr, kr);
-            }
+            Gp::template axpy_col<0, n, true, n>(P, dr, kr);
             x = fma(kr, v, x);             // :374-375
             sigma = fma(v * v, rf, sigma); // :377
             // detf += log f (:378): accumulate prod f as mantissa * 2^exp
@@ -440,113 +327,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 6
             }
             fmin_seen = min_f64(fmin_seen, f);
         };
-        if constexpr (WIDE && MK_WIDE_FILTER_LOOP) {
-            // One model per wavefront: the mask of observed series is wavefront-uniform, so the updates run as a
-            // RUN-TIME loop over its set bits with ONE update body (the series index lives in an SGPR: v_readlane with a
-            // scalar lane select, loadings at a scalar LDS offset, P[j] through a uniform switch) instead of 2 x 32
-            // unrolled bodies -- 64 KB of code whose merged live ranges spilled the covariance row around the masked
-            // path (PMC: 399 GB of traffic per launch against 89 GB algorithmic at configs[3]).
-            unsigned long long m = (unsigned long long)vm;
-            int nupd = 0;
-            while (m) {
-                const int j = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(m));
-                m &= m - 1;
-                double vl = y - x, vl2 = 0.0;
-                sfor<0, K>(MK_LAMBDA(k) { // vl = y_l - x_l - sum_k gam_k x_{N+k}, two chains, factor states from registers
-                    constexpr int kk = decltype(k)::value;
-                    if constexpr (kk % 2 == 0) vl = fma(-gam[kk], xk[kk], vl);
-                    else vl2 = fma(-gam[kk], xk[kk], vl2);
-                });
-                vl += vl2;
-                const double v = readlane_f64(vl, j);
-                double dr = 0.0;
-                switch (j) {
-#define MK_CASE_P(c) \
-    case c:          \
-        if constexpr (c < N) dr = P[c]; \
-        break;
-                    MK_CASE_P(0) MK_CASE_P(1) MK_CASE_P(2) MK_CASE_P(3) MK_CASE_P(4) MK_CASE_P(5) MK_CASE_P(6) MK_CASE_P(7)
-                    MK_CASE_P(8) MK_CASE_P(9) MK_CASE_P(10) MK_CASE_P(11) MK_CASE_P(12) MK_CASE_P(13) MK_CASE_P(14) MK_CASE_P(15)
-                    MK_CASE_P(16) MK_CASE_P(17) MK_CASE_P(18) MK_CASE_P(19) MK_CASE_P(20) MK_CASE_P(21) MK_CASE_P(22) MK_CASE_P(23)
-                    MK_CASE_P(24) MK_CASE_P(25) MK_CASE_P(26) MK_CASE_P(27) MK_CASE_P(28) MK_CASE_P(29) MK_CASE_P(30) MK_CASE_P(31)
-                    MK_CASE_P(32) MK_CASE_P(33) MK_CASE_P(34) MK_CASE_P(35) MK_CASE_P(36) MK_CASE_P(37) MK_CASE_P(38) MK_CASE_P(39)
-                    MK_CASE_P(40) MK_CASE_P(41) MK_CASE_P(42) MK_CASE_P(43) MK_CASE_P(44) MK_CASE_P(45) MK_CASE_P(46) MK_CASE_P(47)
-                    MK_CASE_P(48) MK_CASE_P(49) MK_CASE_P(50) MK_CASE_P(51) MK_CASE_P(52) MK_CASE_P(53) MK_CASE_P(54) MK_CASE_P(55)
-                    MK_CASE_P(56) MK_CASE_P(57) MK_CASE_P(58) MK_CASE_P(59) MK_CASE_P(60) MK_CASE_P(61) MK_CASE_P(62) MK_CASE_P(63)
-#undef MK_CASE_P
-                default: break;
-                }
-                const double *gj = (GTAB ? gtab : dvec) + j * K; // loadings of series j (wavefront-uniform address)
-                sfor<0, K>(MK_LAMBDA(k) {
-                    constexpr int kk = decltype(k)::value;
-                    double g;
-                    if constexpr (GTAB) g = gj[kk];
-                    else g = readlane_f64(gam[kk], j);
-                    dr = fma(P[N + kk], g, dr);
-                });
-                double *dv = dvec2 + (nupd & 1) * NP; // two buffers: no second fence per update
-                dv[r] = dr;
-                double fl = rvar + dr, fl2 = 0.0;
-                double dk[K];
-                sfor<0, K>(MK_LAMBDA(k) { dk[decltype(k)::value] = Gp::template bcast<N + decltype(k)::value>(dr); });
-                sfor<0, K>(MK_LAMBDA(k) {
-                    constexpr int kk = decltype(k)::value;
-                    if constexpr (kk % 2 == 0) fl = fma(dk[kk], gam[kk], fl);
-                    else fl2 = fma(dk[kk], gam[kk], fl2);
-                });
-                fl += fl2;
-                const double f = readlane_f64(fl, j);
-                const double rf = rcp_nr(f);
-                const double kr = dr * rf;
-                if constexpr (OUT == 3 && !SYM) {
-                    // the recording pass of the adjoint gradient: (d, 1/f, v) of this update into slot nupd of the step's block of the
-                    // update tape -- what the backward walk would otherwise recompute from the filtered record of step t - 1 (round 6)
-                    if (a.upd) {
-                        double *ub = a.upd + (inst * a.bs + t * a.ts) * a.us + (long)nupd * adjoint_update_slot_c(N, K);
-                        ub[r] = dr;                                  // one 8 n-byte run per update
-                        if (lead) *reinterpret_cast<v2d *>(ub + NP) = v2d{rf, v};
-                    }
-                }
-                wave_lds_sync();
-                {
-                    double dc[n];
-                    load_row<n>(dv, dc);
-#pragma unroll
-                    for (int c = 0; c < n; ++c) P[c] = fma(-dc[c], kr, P[c]);
-                }
-                if constexpr (TAPE) {
-                    // tape entry of the observed series j: [ kt = T k | v/f | 1/f | y_j | 0 ], the gain in the observable basis
-                    // (kt_l = k_l + sum_k g_lk k_{N+k} on the series lanes, the factor gains themselves on the factor lanes:
-                    // one 8 n-byte run), as filter_split_kernel writes it
-                    double kt = 0.0;
-                    sfor<0, K>(MK_LAMBDA(k) { kt = fma(gam[decltype(k)::value], Gp::template bcast<N + decltype(k)::value>(kr), kt); });
-                    kt = lane < N ? kr + kt : kr;
-                    trec[j * XS + r] = kt;
-                    const double yj = readlane_f64(y, j);
-                    if (lead) {
-                        double *sd = trec + j * XS + n;
-                        sd[0] = v * rf;
-                        sd[1] = rf;
-                        sd[2] = yj;
-                        sd[3] = 0.0;
-                    }
-                }
-                sfor<0, K>(MK_LAMBDA(k) { // factor-state replicas: gain elements of lanes N+k (off the critical path)
-                    constexpr int kk = decltype(k)::value;
-                    xk[kk] = fma(Gp::template bcast<N + kk>(kr), v, xk[kk]);
-                });
-                x = fma(kr, v, x);
-                sigma = fma(v * v, rf, sigma);
-                fmant *= f;
-                if ((++nupd & 3) == 0) { // keep the product of innovation variances normalised (exact: powers of two)
-                    fexp += __builtin_amdgcn_frexp_exp(fmant);
-                    fmant = __builtin_amdgcn_frexp_mant(fmant);
-                }
-                fmin_seen = min_f64(fmin_seen, f);
-            }
-            fexp += __builtin_amdgcn_frexp_exp(fmant);
-            fmant = __builtin_amdgcn_frexp_mant(fmant);
-        } else if (ball == Gp::full_mask(N)) { // every model of this wavefront observes all N series: no masking
+        if (ball == Gp::full_mask(N)) { // every model of this wavefront observes all N series: no masking
             sfor<0, N>(MK_LAMBDA(jc) {
                 update(jc);
                 slot(jc);
@@ -564,10 +345,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 6
         }
 
         const int cnt = __popcll((unsigned long long)vm);
-        double pad = 0.0; // records: what this lane writes into its pad slot of the filtered record
         // undeferred logarithm: the scattered pad store below may go to the record of step t - 1, whose last chunk store
         // (slot N) must precede it in program order
-        if constexpr (FDEFER && !FDLOG) slot(std::integral_constant<int, N>{});
+        if constexpr (RECF && !FDLOG) slot(std::integral_constant<int, N>{});
         if constexpr (FDLOG) {
             // deferred: the logarithm, the pad and the running sums of this step are formed at the head of the next one
             // (carried_book), with this step's own sc
@@ -579,16 +359,383 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 6
         } else if (cnt > 0) { // :380-382 compressed bookkeeping
             if constexpr (BOOK) {
                 int le = 0;
-                const double lm = MK_TUNE_SKIP(a, 4) ? 0.5 : log_mant(fmant, le); // (timing build: a constant in the pad)
-                const double detf = MK_TUNE_SKIP(a, 4) ? lm : fma((double)(fexp + le), kLn2, lm);
+                const double lm = log_mant(fmant, le);
+                const double detf = fma((double)(fexp + le), kLn2, lm);
                 if constexpr (RECF) {
                     // compressed entry sc lives in the pad of filtered record sc; sc == t unless an earlier
                     // step of this model was empty (then: one scattered 16-byte store, rare)
                     if (sc == t) {
-                        pad = pslot == 0 ? sigma : (pslot == 1 ? detf : 0.0);
                         pad0 = sigma;
                         pad1 = detf;
                     } else if (lead && a.sigmas)
+                        *reinterpret_cast<v2d *>(a.F + (inst * a.bs + sc * a.ts) * RS + NVO) = v2d{sigma, detf};
+                } else {
+                    if (a.sigmas && lead) a.sigmas[(inst * a.bs + sc * a.ts) * a.sig_stride] = sigma;
+                    if (a.detfs && lead) a.detfs[(inst * a.bs + sc * a.ts) * a.sig_stride] = detf;
+                }
+                if (sc >= a.warmup) { // get_mle: detfs[warmup:], sigmas[warmup:] are COMPRESSED indices (:563-564)
+                    sum_det += detf;
+                    sum_sig += sigma;
+                }
+            } else {
+                if (sc >= a.warmup) {
+                    sum_sig += sigma;
+                    run_mant *= fmant;
+                    run_exp += fexp + __builtin_amdgcn_frexp_exp(run_mant);
+                    run_mant = __builtin_amdgcn_frexp_mant(run_mant);
+                }
+            }
+            ++sc;
+        }
+        if (t >= a.warmup) nobs += cnt; // observation_count[warmup:] is a TIME index (:565)
+
+        if constexpr (RECF) {
+            RIO::put(imgF, gw, r, x, P); // :389-390; leaves in the next step (the last one: after the loop)
+            if constexpr (!FDLOG) {
+                RIO::put_pad(imgF, gw, pad0, pad1);
+                pad0 = pad1 = 0.0;
+            }
+            if constexpr (FDLOG) slot(std::integral_constant<int, N>{}); // the last chunk(s), gathered behind the last update
+            if constexpr (OUT == 1) recP += rstep;
+            recFc = recF;
+            recF += rstep;
+        } else if constexpr (OUT == 2) {
+            if (oF.vec) *oF.vec = x;
+            if (oF.mat) store_cols<n>(oF.mat, P);
+            oF.advance(1);
+        }
+    }
+    }
+
+    if constexpr (RECF) {
+        if (T > 0) { // the last step's bookkeeping and its filtered record
+            if constexpr (FDLOG) carried_book(T - 1);
+            RIO::emit(imgF, recFc, rmap);
+        }
+    }
+    // zero tail of the compressed arrays (np.zeros init, :307-308); record pads were written as zeros
+    if (BOOK && !RECF) {
+        for (long i = sc + lane; i < T; i += G) {
+            if (a.sigmas) a.sigmas[(inst * a.bs + i * a.ts) * a.sig_stride] = 0.0;
+            if (a.detfs) a.detfs[(inst * a.bs + i * a.ts) * a.sig_stride] = 0.0;
+        }
+    }
+    if (lead) {
+        if (!BOOK) sum_det = fma((double)run_exp, kLn2, log(run_mant));
+        // an invalid model -- an innovation variance f <= 0, or a NaN one -- gets a NaN objective and the flag: the product of the f's
+        // loses the sign of an even number of negative ones, and v_min_f64 skips a NaN operand, but a NaN f makes every gain and with
+        // it the state NaN for good
+        const bool bad_f = !(fmin_seen > 0.0) || x != x;
+        if (a.mle) a.mle[inst] = bad_f ? __builtin_nan("") : ((double)nobs * kLog2Pi + sum_det) + sum_sig; // :566
+        if (a.sigmacount) a.sigmacount[inst] = sc;
+        if (a.status) a.status[inst] = bad_f ? MK_FLAG_NONPOSITIVE_F : 0u;
+    }
+}
+
+// P[c] of the lane's row for a wavefront-uniform c < N (the column lives in a named register: a uniform jump, no movrel)
+template <int N, int n>
+__device__ __forceinline__ double pick_series_column(const double (&P)[n], int j)
+{
+    double dr = 0.0;
+    switch (j) {
+#define MK_CASE_P(c) \
+    case c:          \
+        if constexpr (c < N) dr = P[c]; \
+        break;
+        MK_CASE_P(0) MK_CASE_P(1) MK_CASE_P(2) MK_CASE_P(3) MK_CASE_P(4) MK_CASE_P(5) MK_CASE_P(6) MK_CASE_P(7)
+        MK_CASE_P(8) MK_CASE_P(9) MK_CASE_P(10) MK_CASE_P(11) MK_CASE_P(12) MK_CASE_P(13) MK_CASE_P(14) MK_CASE_P(15)
+        MK_CASE_P(16) MK_CASE_P(17) MK_CASE_P(18) MK_CASE_P(19) MK_CASE_P(20) MK_CASE_P(21) MK_CASE_P(22) MK_CASE_P(23)
+        MK_CASE_P(24) MK_CASE_P(25) MK_CASE_P(26) MK_CASE_P(27) MK_CASE_P(28) MK_CASE_P(29) MK_CASE_P(30) MK_CASE_P(31)
+        MK_CASE_P(32) MK_CASE_P(33) MK_CASE_P(34) MK_CASE_P(35) MK_CASE_P(36) MK_CASE_P(37) MK_CASE_P(38) MK_CASE_P(39)
+        MK_CASE_P(40) MK_CASE_P(41) MK_CASE_P(42) MK_CASE_P(43) MK_CASE_P(44) MK_CASE_P(45) MK_CASE_P(46) MK_CASE_P(47)
+        MK_CASE_P(48) MK_CASE_P(49) MK_CASE_P(50) MK_CASE_P(51) MK_CASE_P(52) MK_CASE_P(53) MK_CASE_P(54) MK_CASE_P(55)
+        MK_CASE_P(56) MK_CASE_P(57) MK_CASE_P(58) MK_CASE_P(59) MK_CASE_P(60) MK_CASE_P(61) MK_CASE_P(62) MK_CASE_P(63)
+#undef MK_CASE_P
+    default: break;
+    }
+    return dr;
+}
+
+// ---- the one-model-per-wavefront filter (16 < n <= 64, "lane per state"): lane r owns state r; the scalar updates run as a
+// run-time loop over the observed series ----
+// resident wavefronts per SIMD asked of the compiler: two only while the two n-double row arrays fit 256 VGPRs
+// (compile-checked at n = 64, the constraint spilled 1.1 KB per lane)
+#ifndef MK_WIDE_FILTER_WAVES
+#define MK_WIDE_FILTER_WAVES 2
+#endif
+template <int N, int K, int OUT, bool BOOK, bool SYM>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(N + K <= 40 ? MK_WIDE_FILTER_WAVES : 1))) filter_wave_kernel(FilterArgs a)
+{
+    static_assert(!SYM || OUT == 1 || OUT == 3, "packed-symmetric layout applies to record outputs");
+    constexpr int n = N + K, G = 64;
+    static_assert(n > 16 && n <= G, "state dimension must fit the wavefront; n <= 16 is filter_kernel's");
+    constexpr bool TAPE = (OUT == 4);
+    static_assert(!TAPE || N * K > 32, "the tape writer reads the loadings from their LDS table");
+    using Gp = Group<G>;
+    constexpr int GPB = 256 / G; // models per 256-thread workgroup
+    constexpr bool HOIST = (N * K <= 32); // few enough loadings to pick with 2 K v_readlane per update
+    constexpr int NV = record_payload(n);
+    const int lane = threadIdx.x % G;
+    long inst = (long)blockIdx.x * GPB + threadIdx.x / G;
+    if (inst > a.B - 1) inst = a.B - 1; // surplus wavefronts replicate the last model (identical stores)
+    const long rec = inst % a.R;
+    const int r = lane < n ? lane : n - 1; // lanes >= n replicate lane n-1
+    const bool lead = lane == 0;
+    const long T = a.T;
+
+    // per-model constants: lane r holds phi_r, q_r; lane j < N holds loadings[j,:] and obsvar[j]
+    const double phi_r = a.phi[inst * n + r];
+    const double q_r = a.q[inst * n + r];
+    // row r of Phi (x) Phi and of Q = diag(q) would be 4n VGPRs, which is what stands between one and two resident
+    // wavefronts per SIMD: diag(Phi) is read back from LDS every step (wavefront-uniform address) and Q's row is re-selected
+    constexpr int NP = n + (n & 1); // even: rows of 16-byte pieces
+    __shared__ __attribute__((aligned(16))) double lds_phi[(256 / G) * 3 * NP];
+    double *phim = lds_phi + (threadIdx.x / G) * 3 * NP; // diag(Phi)
+    double *dvec = phim + NP;                            // d = P Z_j^T of the current update: two buffers, alternating
+    phim[r] = phi_r;
+    wave_lds_sync();
+    const int jr = lane < N ? lane : N - 1;
+    double gam[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) gam[k] = a.loadings[(rec * N + jr) * K + k];
+    const double rvar = a.obsvar ? a.obsvar[rec * N + jr] : 0.0;
+    // too many loadings for readlanes: a wave-private LDS copy read at wavefront-uniform addresses (two 16-byte reads per
+    // update for K = 4) instead of 2 K v_readlane per update
+    constexpr bool GTAB = !HOIST;
+    __shared__ __attribute__((aligned(16))) double lds_gam[GTAB ? (256 / G) * N * K : 1];
+    double *gtab = lds_gam + (GTAB ? (threadIdx.x / G) * N * K : 0);
+    if constexpr (GTAB) {
+        if (lane < N) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) gtab[lane * K + k] = gam[k];
+        }
+        wave_lds_sync();
+    }
+
+    // initial state (run_filter defaults, kalmanfilter.py:747-750)
+    double x = a.x0 ? a.x0[inst * n + r] : 0.0;
+    double P[n];
+#pragma unroll
+    for (int c = 0; c < n; ++c) P[c] = a.P0 ? a.P0[(inst * n + r) * n + c] : (c == r ? 1.0 : 0.0);
+
+    // the K common-factor states (and their phi) replicated in every lane, updated with the gain elements broadcast at the
+    // END of an update (next to the rank-one update) -- the innovation of the next update then starts from registers
+    // instead of K dependent readlane pairs at the head of its chain
+    double xk[K], phik[K];
+    sfor<0, K>(MK_LAMBDA(k) {
+        xk[decltype(k)::value] = Gp::template bcast<N + decltype(k)::value>(x);
+        phik[decltype(k)::value] = Gp::template bcast<N + decltype(k)::value>(phi_r);
+    });
+
+    // outputs: (b, t) lives at block index b*bs + t*ts -- (T, 1) model-major or (1, B) time-major
+    constexpr bool RECF = (OUT == 1 || OUT == 3); // filtered moments go to packed records
+    MomentPtr oP = moment_ptr<n>(a.Xp, a.Pp, inst * a.bs, a.ts, OUT == 1 ? a.rs : 0, r); // predicted moments
+    MomentPtr oF = moment_ptr<n>(a.F, a.Pf, inst * a.bs, a.ts, RECF ? a.rs : 0, r);      // filtered moments
+    // OUT == 1 (packed records): the RS - NV pad doubles of both records are written too (whole cache
+    // lines): lane l owns pad slot min(l, PADN-1); filtered record: slot 0 = sigma, slot 1 = detf, rest 0
+    // (RS / NVO: stride and payload of the record in HBM -- full-square or packed-symmetric)
+    constexpr int RS = SYM ? record_stride_sym_c(n) : record_stride_c(n), NVO = SYM ? record_payload_sym(n) : NV;
+    constexpr int PADN = RS - NVO;
+    const int pslot = lane < PADN ? lane : PADN - 1;
+    double *padF = RECF ? a.F + inst * a.bs * RS + NVO + pslot : nullptr;
+    double *padP = OUT == 1 ? a.Xp + inst * a.bs * RS + NVO + pslot : nullptr;
+    double sum_sig = 0.0, sum_det = 0.0;
+    long sc = 0; // compressed index of the next observed step
+    // TAPE: block of (model, step) = N (state tape: N + K) entries [ vector in the observable basis (n) | s0 s1 s2 0 ] of
+    // XS = n + 4 doubles (mk_internal.h); lane r < n holds element r of an entry's vector
+    [[maybe_unused]] constexpr int XS = tape_xs_c(N, K);
+    [[maybe_unused]] double *trec = TAPE ? a.F + inst * a.bs * a.rs : nullptr;
+    [[maybe_unused]] const long tstep = a.ts * a.rs;
+
+    // ---- observation stream: tiles of 16 time steps through LDS (see filter_kernel) ----
+    // A step takes ~10 us here, the once-per-tile wait for the store queue is noise, and N staging registers held across
+    // two steps are not: lane l fetches row min(t0 + l, T - 1) of the tile and parks it in one go.
+    constexpr int TS = 16;
+    const int lrow = lane < TS ? lane : TS - 1; // lanes >= TS duplicate row TS-1
+    constexpr bool OV2 = (N % 2 == 0);          // 16-byte row pieces when rows are 16-byte aligned
+    constexpr int ONC = OV2 ? N / 2 : N;
+    using ochunk_t = typename std::conditional<OV2, v2d, double>::type;
+    __shared__ __attribute__((aligned(16))) double lds_obs[(256 / G) * TS * N];
+    double *otile = lds_obs + (threadIdx.x / G) * TS * N; // this model's tile
+    const double *obase = a.obs + rec * a.obs_bs * N;
+    const long ostep = a.obs_ts * N;
+    long otr = 0; // the row this lane fetches for the next tile, formed one tile ahead (where filter_kernel issues its loads)
+    auto obs_row = [&](long t0) __attribute__((always_inline)) {
+        long tr = t0 + lrow;
+        if (tr > T - 1) tr = T - 1;
+        otr = tr;
+    };
+    auto obs_fetch = [&]() __attribute__((always_inline)) { // HBM -> the LDS tile
+        ochunk_t *dst = reinterpret_cast<ochunk_t *>(otile + lrow * N);
+        wave_lds_sync(); // the previous tile's reads are complete
+        const ochunk_t *src = reinterpret_cast<const ochunk_t *>(obase + otr * ostep);
+#pragma unroll
+        for (int i = 0; i < ONC; ++i) dst[i] = src[i];
+        wave_lds_sync();
+    };
+    obs_row(0);
+    double ynext = 0.0;
+
+    double run_mant = 1.0; // !BOOK: prod of f over the counted steps, normalised
+    long run_exp = 0;
+    long nobs = 0;
+    double fmin_seen = 1.0;
+
+    for (long t0 = 0; t0 < T; t0 += TS) {
+    obs_fetch();        // tile t0
+    obs_row(t0 + TS);   // tile t0 + TS (rows clamped to T-1)
+    ynext = otile[jr];
+    const long tend = t0 + TS < T ? t0 + TS : T;
+    for (long t = t0; t < tend; ++t) {
+        const double y = ynext;
+        {
+            // next step's observation from LDS now (latency hidden by this step); the last step of a tile
+            // re-reads its own row, the outer loop supplies the next tile's first
+            const int s1 = (int)(t - t0) + 1;
+            ynext = otile[(s1 < TS ? s1 : TS - 1) * N + jr];
+        }
+        // which series are observed at this step (NaN / inf = missing, kalmanfilter.py:657)
+        const unsigned long long ball = __ballot(lane < N && isfinite(y));
+        const auto vm = Gp::group_bits(ball);
+
+        // ---- predict (:318-331; Phi diagonal) ----
+        x = phi_r * x;
+#pragma unroll
+        for (int k = 0; k < K; ++k) xk[k] = phik[k] * xk[k];
+        {
+            int rv = r; // opaque copies: keeps the n selects inside the loop (hoisted, they are 2n VGPRs)
+            double qv = q_r;
+            asm volatile("" : "+v"(rv), "+v"(qv));
+            double phc[n];
+            load_row<n>(phim, phc);
+#pragma unroll
+            for (int c = 0; c < n; ++c) P[c] = fma(P[c] * phi_r, phc[c], c == rv ? qv : 0.0);
+        }
+        if constexpr (OUT == 1) {
+            *oP.vec = x;               // :332
+            if constexpr (SYM) store_cols_sym<n>(oP.mat - r, P, r);
+            else store_cols<n>(oP.mat, P);  // :333
+            *padP = 0.0;
+            oP.advance_nn(1);
+            padP += a.ts * RS;
+        } else if constexpr (OUT == 2) {
+            if (oP.vec) *oP.vec = x;
+            if (oP.mat) store_cols<n>(oP.mat, P);
+            oP.advance(1);
+        }
+
+        // ---- sequential scalar updates (:341-378), observations in ascending series order ----
+        // The mask of observed series is wavefront-uniform, so the updates run as a RUN-TIME loop over its set bits with ONE
+        // update body (the series index lives in an SGPR: v_readlane with a scalar lane select, loadings at a scalar LDS
+        // offset, P[j] through a uniform switch).  (Unrolled, 2 x 32 bodies were 64 KB of code whose merged live ranges
+        // spilled the covariance row around the masked path -- PMC: 399 GB of traffic per launch against 89 GB algorithmic
+        // at configs[3].)
+        double sigma = 0.0, fmant = 1.0;
+        int fexp = 0;
+        unsigned long long m = (unsigned long long)vm;
+        int nupd = 0;
+        while (m) {
+            const int j = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(m));
+            m &= m - 1;
+            // innovation (:344-347): every lane l < N forms v_l = y_l - Z_l x with ITS loadings; lane j's value is the one used
+            double vl = y - x, vl2 = 0.0;
+            sfor<0, K>(MK_LAMBDA(k) { // vl = y_l - x_l - sum_k gam_k x_{N+k}, two chains, factor states from registers
+                constexpr int kk = decltype(k)::value;
+                if constexpr (kk % 2 == 0) vl = fma(-gam[kk], xk[kk], vl);
+                else vl2 = fma(-gam[kk], xk[kk], vl2);
+            });
+            vl += vl2;
+            const double v = readlane_f64(vl, j);
+            // d = P Z_j^T : lane r computes d_r from its own row (:349-357)
+            double dr = pick_series_column<N>(P, j);
+            const double *gj = (GTAB ? gtab : dvec) + j * K; // loadings of series j (wavefront-uniform address)
+            sfor<0, K>(MK_LAMBDA(k) {
+                constexpr int kk = decltype(k)::value;
+                double g;
+                if constexpr (GTAB) g = gj[kk];
+                else g = readlane_f64(gam[kk], j);
+                dr = fma(P[N + kk], g, dr);
+            });
+            // P -= k k^T f below (:368-372) needs d_c in every lane.  n broadcasts through readlane are 2n VALU + n FMA
+            // issues; through LDS (every lane stores its d_r, then reads the whole vector at a wavefront-uniform address) the
+            // VALU sees only the n FMAs -- these kernels are VALU-issue bound (one f64 wave instruction per 4 cycles)
+            double *dv = dvec + (nupd & 1) * NP; // two buffers: no second fence per update
+            dv[r] = dr;
+            // innovation variance f = R_j + Z_j d (:359-362), formed at lane j from d_j, d_{N+k}
+            double fl = rvar + dr, fl2 = 0.0;
+            double dk[K];
+            sfor<0, K>(MK_LAMBDA(k) { dk[decltype(k)::value] = Gp::template bcast<N + decltype(k)::value>(dr); });
+            sfor<0, K>(MK_LAMBDA(k) {
+                constexpr int kk = decltype(k)::value;
+                if constexpr (kk % 2 == 0) fl = fma(dk[kk], gam[kk], fl);
+                else fl2 = fma(dk[kk], gam[kk], fl2);
+            });
+            fl += fl2;
+            const double f = readlane_f64(fl, j);
+            const double rf = rcp_nr(f);
+            const double kr = dr * rf; // Kalman gain element r (:364-366)
+            if constexpr (OUT == 3 && !SYM) {
+                // the recording pass of the adjoint gradient: (d, 1/f, v) of this update into slot nupd of the step's block of the
+                // update tape -- what the backward walk would otherwise recompute from the filtered record of step t - 1 (round 6)
+                if (a.upd) {
+                    double *ub = a.upd + (inst * a.bs + t * a.ts) * a.us + (long)nupd * adjoint_update_slot_c(N, K);
+                    ub[r] = dr;                                  // one 8 n-byte run per update
+                    if (lead) *reinterpret_cast<v2d *>(ub + NP) = v2d{rf, v};
+                }
+            }
+            wave_lds_sync();
+            {
+                double dc[n];
+                load_row<n>(dv, dc);
+#pragma unroll
+                for (int c = 0; c < n; ++c) P[c] = fma(-dc[c], kr, P[c]);
+            }
+            if constexpr (TAPE) {
+                // tape entry of the observed series j: [ kt = T k | v/f | 1/f | y_j | 0 ], the gain in the observable basis
+                // (kt_l = k_l + sum_k g_lk k_{N+k} on the series lanes, the factor gains themselves on the factor lanes:
+                // one 8 n-byte run), as filter_split_kernel writes it
+                double kt = 0.0;
+                sfor<0, K>(MK_LAMBDA(k) { kt = fma(gam[decltype(k)::value], Gp::template bcast<N + decltype(k)::value>(kr), kt); });
+                kt = lane < N ? kr + kt : kr;
+                trec[j * XS + r] = kt;
+                const double yj = readlane_f64(y, j);
+                if (lead) {
+                    double *sd = trec + j * XS + n;
+                    sd[0] = v * rf;
+                    sd[1] = rf;
+                    sd[2] = yj;
+                    sd[3] = 0.0;
+                }
+            }
+            sfor<0, K>(MK_LAMBDA(k) { // factor-state replicas: gain elements of lanes N+k (off the critical path)
+                constexpr int kk = decltype(k)::value;
+                xk[kk] = fma(Gp::template bcast<N + kk>(kr), v, xk[kk]);
+            });
+            x = fma(kr, v, x);             // :374-375
+            sigma = fma(v * v, rf, sigma); // :377
+            fmant *= f;                    // detf += log f (:378): accumulate prod f as mantissa * 2^exp
+            if ((++nupd & 3) == 0) { // keep the product of innovation variances normalised (exact: powers of two)
+                fexp += __builtin_amdgcn_frexp_exp(fmant);
+                fmant = __builtin_amdgcn_frexp_mant(fmant);
+            }
+            fmin_seen = min_f64(fmin_seen, f);
+        }
+        fexp += __builtin_amdgcn_frexp_exp(fmant);
+        fmant = __builtin_amdgcn_frexp_mant(fmant);
+
+        const int cnt = __popcll((unsigned long long)vm);
+        double pad = 0.0; // records: what this lane writes into its pad slot of the filtered record
+        if (cnt > 0) { // :380-382 compressed bookkeeping
+            if constexpr (BOOK) {
+                int le = 0;
+                const double lm = log_mant(fmant, le);
+                const double detf = fma((double)(fexp + le), kLn2, lm);
+                if constexpr (RECF) {
+                    // compressed entry sc lives in the pad of filtered record sc; sc == t unless an earlier
+                    // step of this model was empty (then: one scattered 16-byte store, rare)
+                    if (sc == t)
+                        pad = pslot == 0 ? sigma : (pslot == 1 ? detf : 0.0);
+                    else if (lead && a.sigmas)
                         *reinterpret_cast<v2d *>(a.F + (inst * a.bs + sc * a.ts) * RS + NVO) = v2d{sigma, detf};
                 } else {
                     if (a.sigmas && lead) a.sigmas[(inst * a.bs + sc * a.ts) * a.sig_stride] = sigma;
@@ -640,16 +787,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 6
             while (um) {
                 const int u = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(um));
                 um &= um - 1;
-                double dr = 0.0;
-                switch (u) {
-#define MK_CASE_PU(c) \
-    case c:           \
-        if constexpr (c < N) dr = P[c]; \
-        break;
-                    MK_CASE_PU(0) MK_CASE_PU(1) MK_CASE_PU(2) MK_CASE_PU(3) MK_CASE_PU(4) MK_CASE_PU(5) MK_CASE_PU(6) MK_CASE_PU(7) MK_CASE_PU(8) MK_CASE_PU(9) MK_CASE_PU(10) MK_CASE_PU(11) MK_CASE_PU(12) MK_CASE_PU(13) MK_CASE_PU(14) MK_CASE_PU(15) MK_CASE_PU(16) MK_CASE_PU(17) MK_CASE_PU(18) MK_CASE_PU(19) MK_CASE_PU(20) MK_CASE_PU(21) MK_CASE_PU(22) MK_CASE_PU(23) MK_CASE_PU(24) MK_CASE_PU(25) MK_CASE_PU(26) MK_CASE_PU(27) MK_CASE_PU(28) MK_CASE_PU(29) MK_CASE_PU(30) MK_CASE_PU(31) MK_CASE_PU(32) MK_CASE_PU(33) MK_CASE_PU(34) MK_CASE_PU(35) MK_CASE_PU(36) MK_CASE_PU(37) MK_CASE_PU(38) MK_CASE_PU(39) MK_CASE_PU(40) MK_CASE_PU(41) MK_CASE_PU(42) MK_CASE_PU(43) MK_CASE_PU(44) MK_CASE_PU(45) MK_CASE_PU(46) MK_CASE_PU(47) MK_CASE_PU(48) MK_CASE_PU(49) MK_CASE_PU(50) MK_CASE_PU(51) MK_CASE_PU(52) MK_CASE_PU(53) MK_CASE_PU(54) MK_CASE_PU(55) MK_CASE_PU(56) MK_CASE_PU(57) MK_CASE_PU(58) MK_CASE_PU(59) MK_CASE_PU(60) MK_CASE_PU(61) MK_CASE_PU(62) MK_CASE_PU(63)
-#undef MK_CASE_PU
-                default: break;
-                }
+                double dr = pick_series_column<N>(P, u);
                 const double *gu = gtab + u * K;
                 sfor<0, K>(MK_LAMBDA(k) { dr = fma(P[N + decltype(k)::value], gu[decltype(k)::value], dr); });
                 double pt = 0.0;
@@ -668,57 +806,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 6
             trec += tstep;
         }
 
-        if constexpr (FDEFER) {
-            RIO::put(imgF, gw, r, x, P); // leaves in the next step (the last one: after the loop)
-            if constexpr (!FDLOG) {
-                RIO::put_pad(imgF, gw, pad0, pad1);
-                pad0 = pad1 = 0.0;
-            }
-            if constexpr (FDLOG) slot(std::integral_constant<int, N>{}); // the last chunk(s), gathered behind the last update
-            if constexpr (OUT == 1) recP += rstep;
-            recFc = recF;
-            recF += rstep;
-        } else if constexpr (LDSOUT) {
-            RIO::put(imgF, gw, r, x, P);
-            RIO::put_pad(imgF, gw, pad0, pad1);
-            pad0 = pad1 = 0.0;
-            if constexpr (MK_TUNE_SKIP(a, 1) || MK_TUNE_SKIP(a, 2)) {
-                // timing builds of the undeferred form (results meaningless): 1 = the LDS writes and reads without the global
-                // stores, 2 = the stores fed from registers (this lane's row) without the LDS round trip
-                typename RIO::chunk_t tP[FPER], tF[FPER];
-                if constexpr (MK_TUNE_SKIP(a, 2)) {
-#pragma unroll
-                    for (int m = 0; m < FPER; ++m) tP[m] = tF[m] = typename RIO::chunk_t{P[(2 * m) % n], P[(2 * m + 1) % n]};
-                } else {
-                    wave_lds_sync();
-#pragma unroll
-                    for (int m = 0; m < FPER; ++m) {
-                        if constexpr (OUT == 1) tP[m] = RIO::gather(imgP, rmap, m);
-                        tF[m] = RIO::gather(imgF, rmap, m);
-                    }
-                }
-#pragma unroll
-                for (int m = 0; m < FPER; ++m) {
-                    if constexpr (MK_TUNE_SKIP(a, 1)) {
-                        if constexpr (OUT == 1) asm volatile("" ::"v"(tP[m]));
-                        asm volatile("" ::"v"(tF[m]));
-                    } else {
-                        if constexpr (OUT == 1) RIO::store_one(recP, rmap, m, tP[m]);
-                    }
-                }
-                if constexpr (!MK_TUNE_SKIP(a, 1)) {
-#pragma unroll
-                    for (int m = 0; m < FPER; ++m) RIO::store_one(recF, rmap, m, tF[m]);
-                }
-                if constexpr (OUT == 1) recP += rstep;
-            } else if constexpr (OUT == 1) {
-                RIO::emit2(imgP, recP, imgF, recF, rmap);
-                recP += rstep;
-            } else {
-                RIO::emit(imgF, recF, rmap);
-            }
-            recF += rstep;
-        } else if constexpr (RECF) {
+        if constexpr (RECF) {
             *oF.vec = x;               // :389
             if constexpr (SYM) store_cols_sym<n>(oF.mat - r, P, r);
             else store_cols<n>(oF.mat, P);  // :390
@@ -733,12 +821,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 6
     }
     }
 
-    if constexpr (FDEFER) {
-        if (T > 0) { // the last step's bookkeeping and its filtered record
-            if constexpr (FDLOG) carried_book(T - 1);
-            RIO::emit(imgF, recFc, rmap);
-        }
-    }
     // zero tail of the compressed arrays (np.zeros init, :307-308); record pads were written as zeros
     if (BOOK && !RECF) {
         for (long i = sc + lane; i < T; i += G) {
@@ -748,10 +830,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(G == 6
     }
     if (lead) {
         if (!BOOK) sum_det = fma((double)run_exp, kLn2, log(run_mant));
-        // an invalid model -- an innovation variance f <= 0, or a NaN one -- gets a NaN objective and the flag: the product of the f's
-        // loses the sign of an even number of negative ones, and v_min_f64 skips a NaN operand, but a NaN f makes every gain and with
-        // it the state NaN for good
-        const bool bad_f = !(fmin_seen > 0.0) || x != x;
+        const bool bad_f = !(fmin_seen > 0.0) || x != x; // as in filter_kernel: f <= 0 or NaN -> NaN objective and the flag
         if (a.mle) a.mle[inst] = bad_f ? __builtin_nan("") : ((double)nobs * kLog2Pi + sum_det) + sum_sig; // :566
         if (a.sigmacount) a.sigmacount[inst] = sc;
         if (a.status) a.status[inst] = bad_f ? MK_FLAG_NONPOSITIVE_F : 0u;
@@ -2326,6 +2405,13 @@ __global__ void sum_kernel(long count, const double *v, double *out)
 // =====================================================================================
 // Shape registry and launchers
 // =====================================================================================
+// the filter of one output form: a 16-lane group per model up to n = 16, one model per wavefront above
+template <int N, int K, int OUT, bool BOOK, bool SYM>
+static void launch_filter_form(const FilterArgs &a, unsigned grid, hipStream_t s)
+{
+    if constexpr (N + K <= 16) hipLaunchKernelGGL((filter_kernel<N, K, 16, OUT, BOOK, SYM>), dim3(grid), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((filter_wave_kernel<N, K, OUT, BOOK, SYM>), dim3(grid), dim3(256), 0, s, a);
+}
 template <int N, int K>
 static hipError_t launch_filter_nk(const FilterArgs &a, hipStream_t s)
 {
@@ -2352,29 +2438,29 @@ static hipError_t launch_filter_nk(const FilterArgs &a, hipStream_t s)
             if (e != hipErrorNotSupported) return e;
         }
     }
-    if constexpr (n > 16 && N > 32) { // the backward tape of the shapes beyond the split layout: the lane-per-state loop filter writes it
+    if constexpr (n > 16 && N > 32) { // the backward tape of the shapes beyond the split layout: filter_wave_kernel writes it
         if (a.tape) {
-            if (book) hipLaunchKernelGGL((filter_kernel<N, K, G, 4, true, false>), dim3(grid), dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((filter_kernel<N, K, G, 4, false, false>), dim3(grid), dim3(256), 0, s, a);
+            if (book) launch_filter_form<N, K, 4, true, false>(a, grid, s);
+            else launch_filter_form<N, K, 4, false, false>(a, grid, s);
             return hipGetLastError();
         }
     } else if (a.tape) {
         return hipErrorNotSupported;
     }
     if (!any && !book)
-        hipLaunchKernelGGL((filter_kernel<N, K, G, 0, false, false>), dim3(grid), dim3(256), 0, s, a);
+        launch_filter_form<N, K, 0, false, false>(a, grid, s);
     else if (!any)
-        hipLaunchKernelGGL((filter_kernel<N, K, G, 0, true, false>), dim3(grid), dim3(256), 0, s, a);
+        launch_filter_form<N, K, 0, true, false>(a, grid, s);
     else if (a.rs > 0 && a.Xp && a.sym) // packed-symmetric records
-        hipLaunchKernelGGL((filter_kernel<N, K, G, 1, true, true>), dim3(grid), dim3(256), 0, s, a);
+        launch_filter_form<N, K, 1, true, true>(a, grid, s);
     else if (a.rs > 0 && a.Xp) // packed records (validated by the C ABI): whole-cache-line stores
-        hipLaunchKernelGGL((filter_kernel<N, K, G, 1, true, false>), dim3(grid), dim3(256), 0, s, a);
+        launch_filter_form<N, K, 1, true, false>(a, grid, s);
     else if (a.rs > 0 && a.sym) // filtered record only
-        hipLaunchKernelGGL((filter_kernel<N, K, G, 3, true, true>), dim3(grid), dim3(256), 0, s, a);
+        launch_filter_form<N, K, 3, true, true>(a, grid, s);
     else if (a.rs > 0)
-        hipLaunchKernelGGL((filter_kernel<N, K, G, 3, true, false>), dim3(grid), dim3(256), 0, s, a);
+        launch_filter_form<N, K, 3, true, false>(a, grid, s);
     else
-        hipLaunchKernelGGL((filter_kernel<N, K, G, 2, true, false>), dim3(grid), dim3(256), 0, s, a);
+        launch_filter_form<N, K, 2, true, false>(a, grid, s);
     return hipGetLastError();
 }
 

@@ -3,7 +3,7 @@
 // Reference semantics: seqkalmanfilter, /root/reference/metran/kalmanfilter.py:236-400 (predict :318-333, scalar
 // updates :341-378, compressed bookkeeping :380-382, filtered moments :384-390) and get_mle (:550-567).
 //
-// Why.  filter_kernel<N,K,64> gives every state a lane: at configs[3] (32 series + 4 factors) 36 of the 64 lanes carry
+// Why.  filter_wave_kernel<N,K> (mk_kernels.hip) gives every state a lane: at configs[3] (32 series + 4 factors) 36 of the 64 lanes carry
 // data and a wavefront serves ONE model; the kernel is bound by VALU issue (round-2 counters: 2 467 VALU instructions
 // per model-step, the f64 rank-one update alone is n of them per observation), so the 28 idle lanes are 44 % of the
 // machine.  Metran's state vector is [series states | factor states] (metran.py:283-370) and every covariance is
@@ -25,7 +25,7 @@
 // read (mk_prims.h): rows 0 .. n-1, columns < N through the symmetric column runs of the series rows; columns >= N of
 // the series rows as K contiguous doubles per lane; the factor block from the replicated copy.
 // Modes: OUT 0 (objective only), 1 (predicted + filtered records), 3 (filtered record), full-square or (SYM, round 4)
-// packed-symmetric records; dense outputs keep filter_kernel<N,K,64>.
+// packed-symmetric records; dense outputs keep filter_wave_kernel<N,K>.
 // OUT 4 (round 4): the BACKWARD TAPE of the inverse-free smoother (mk_dk.hip) instead of a covariance record -- per
 // (step, series) one entry of n + 4 doubles in the OBSERVABLE basis xt = T x, T = [[I, G], [0, I]] (series states
 // replaced by the observables y_j = x_j + sum_k g_jk x_{N+k}, in which the observation rows are unit vectors):
@@ -1270,7 +1270,7 @@ hipError_t launch_split_nk(const FilterArgs &a, hipStream_t s)
         const unsigned grid = (unsigned)((a.B + M - 1) / M);
         const bool book = a.sigmas || a.detfs;
         const bool any = a.F || a.Pf || a.Xp || a.Pp;
-        if (a.sym) { // packed-symmetric records (round 4; before: filter_kernel<N,K,64>)
+        if (a.sym) { // packed-symmetric records (round 4; before: the one-model-per-wavefront filter)
             if (a.rs > 0 && a.Xp) hipLaunchKernelGGL((filter_split_kernel<N, K, H, 1, true, true>), dim3(grid), dim3(64), 0, s, a);
             else if (a.rs > 0 && any) hipLaunchKernelGGL((filter_split_kernel<N, K, H, 3, true, true>), dim3(grid), dim3(64), 0, s, a);
             else return hipErrorNotSupported;
@@ -1290,7 +1290,7 @@ hipError_t launch_split_nk(const FilterArgs &a, hipStream_t s)
         else if (!any) hipLaunchKernelGGL((filter_split_kernel<N, K, H, 0, true>), dim3(grid), dim3(64), 0, s, a);
         else if (a.rs > 0 && a.Xp) hipLaunchKernelGGL((filter_split_kernel<N, K, H, 1, true>), dim3(grid), dim3(64), 0, s, a);
         else if (a.rs > 0) hipLaunchKernelGGL((filter_split_kernel<N, K, H, 3, true>), dim3(grid), dim3(64), 0, s, a);
-        else return hipErrorNotSupported; // dense outputs: filter_kernel<N,K,64>
+        else return hipErrorNotSupported; // dense outputs: filter_wave_kernel<N,K>
         return hipGetLastError();
     } else {
         return hipErrorNotSupported;
@@ -1314,7 +1314,7 @@ namespace mk {
 //   n + 1 filter runs (metran/solver.py:248-255) -- 37 of them at configs[3]'s shape.
 // =====================================================================================
 // UPD (round 6): the (d, 1/f, v) of every update are not recomputed but READ from the update tape the recording forward pass wrote
-// (FilterArgs.upd: filter_kernel<N,K,64,OUT=3>, one block of N slots per (model, step)) -- the forward half of a step was 38 % of this
+// (FilterArgs.upd: filter_wave_kernel<N,K,OUT=3>, one block of N slots per (model, step)) -- the forward half of a step was 38 % of this
 // kernel's instructions, and the walk is one wavefront's dependent chain.  The step's block is copied HBM -> LDS by the wavefront
 // itself (global_load_lds, asynchronous, no registers), issued when the previous block's last slot has been consumed.
 typedef __attribute__((address_space(3))) void adj_lds_void_t;

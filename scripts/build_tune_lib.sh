@@ -1,8 +1,6 @@
 #!/bin/bash
 # A timing build of libmetran_hip.so: one kernel file (default mk_split.hip) recompiled with -DMK_TUNE=<mask> (mk_internal.h; wrong
 # results, timing only), linked with the objects of the last `make`.   [EXTRA="-D..."] bash scripts/build_tune_lib.sh <mask> <out.so> [file]
-# mk_kernels (filter_kernel's record emission, undeferred form: EXTRA=-DMK_FILTER_DEFER=0): 1 = LDS writes and reads without the global
-# stores, 2 = the stores fed from registers without the LDS round trip, 4 = no per-step logarithm (a constant in the pad)
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd); T=$1; OUT=$2; SRC=${3:-mk_split}
 B=/tmp/tune_${T}_$(echo "$SRC $EXTRA" | md5sum | cut -c1-8); mkdir -p $B

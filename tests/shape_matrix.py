@@ -18,30 +18,32 @@ WAVE_SMOOTHER_MAX_N = 51   # mk_internal.h: wave_smoother_max_n
 
 # file:line as of this writing; the text, not the line number, is what tests/test_shape_matrix.py holds the source to
 SWITCHES = {
-    # mk_kernels.hip:2119 (launch_filter_nk) / :2174 (launch_smoother_nk): a 16-lane group per model, else one wavefront
+    # mk_kernels.hip:2419 (launch_filter_nk: filter_kernel, else filter_wave_kernel) / :2474 (launch_smoother_nk): a 16-lane group
+    # per model, else one wavefront
     "narrow": ("all", lambda N, K: N + K <= 16, "mk_kernels.hip",
                "constexpr int G = n <= 16 ? 16 : 64;", "n <= 16"),
-    # mk_kernels.hip:2181: smoother_blk_kernel (the MFMA record smoother of the narrow models) exists for n <= 15 only
+    # mk_kernels.hip:2481: smoother_blk_kernel (the MFMA record smoother of the narrow models) exists for n <= 15 only
     "blk": ("narrow", lambda N, K: N + K <= 15, "mk_kernels.hip", "if constexpr (n <= 15) {", "n <= 15"),
-    # mk_kernels.hip:62 (filter_kernel) / :1566 (sparse objective): Z's loading block replicated in registers
+    # mk_kernels.hip:81 (filter_kernel) / :1818 (sparse objective): Z's loading block replicated in registers; :476
+    # (filter_wave_kernel): the loadings picked by readlanes, beyond that from an LDS table
     "HOIST": ("all", lambda N, K: N * K <= 32, "mk_kernels.hip",
               "constexpr bool HOIST = (N * K <= 32);", "(N * K <= 32)"),
-    # mk_split.hip:1266 (launch_split_nk): the split layout (and the tape writer filter_obs_kernel) serves N <= 32
+    # mk_split.hip:1268 (launch_split_nk): the split layout (and the tape writer filter_obs_kernel) serves N <= 32
     "split": ("wide", lambda N, K: N <= 32, "mk_split.hip", "if constexpr (N + K > 16 && N <= 32) {", "N + K > 16 && N <= 32"),
-    # mk_split.hip:1267: H lanes per model
+    # mk_split.hip:1269: H lanes per model
     "H16": ("split", lambda N, K: N <= 16, "mk_split.hip",
             "constexpr int H = N <= 16 ? 16 : 32, M = 64 / H;", "N <= 16"),
-    # mk_split.hip:175 (filter_split_kernel) / :719 (filter_obs_kernel): 16-byte factor parts and entry scalars
+    # mk_split.hip:175 (filter_split_kernel) / :720 (filter_obs_kernel): 16-byte factor parts and entry scalars
     "PAIRS": ("split", lambda N, K: K % 2 == 0 and N % 2 == 0, "mk_split.hip",
               "constexpr bool PAIRS = (K % 2 == 0 && N % 2 == 0);", "(K % 2 == 0 && N % 2 == 0)"),
-    # mk_split.hip:737 (filter_obs_kernel): the factor block and means one element per lane, read back in 16-byte pairs
+    # mk_split.hip:738 (filter_obs_kernel): the factor block and means one element per lane, read back in 16-byte pairs
     "DIST": ("split", lambda N, K: dist(N, K), "mk_split.hip",
              "constexpr bool DIST = (KF + K <= H) && (K % 2 == 0) && !MK_TUNE_SKIP(a, 512);",
              "(KF + K <= H) && (K % 2 == 0) && !MK_TUNE_SKIP(a, 512)"),
-    # mk_split.hip:739: an odd KF + K makes the last pair DIST reads back (:924, :1170) half padding -- not a switch of its
+    # mk_split.hip:740: an odd KF + K makes the last pair DIST reads back (:924, :1170) half padding -- not a switch of its
     # own (no C expression), a case of DIST the matrix must hold both sides of
     "DIST_odd": ("dist", lambda N, K: (kf(K) + K) % 2 == 1, "mk_split.hip", "constexpr int FV = (KF + K + 1) & ~1;", None),
-    # mk_kernels.hip:2141 (launch_filter_nk): the lane-per-state filter writes the tape of the models beyond the split layout
+    # mk_kernels.hip:2441 (launch_filter_nk): filter_wave_kernel (lane per state) writes the tape of the models beyond the split layout
     "lps_tape": ("wide", lambda N, K: N > 32, "mk_kernels.hip", "if constexpr (n > 16 && N > 32) {", "n > 16 && N > 32"),
     # mk_wide.hip:276 (smoother_mfma_kernel): the rows of A folded into the lanes the model does not use
     "FOLD": ("wide", lambda N, K: N + K <= 36, "mk_wide.hip", "constexpr bool FOLD = FOLDP && n <= 36;", "FOLDP && n <= 36"),

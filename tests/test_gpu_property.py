@@ -92,7 +92,7 @@ def test_filter_smooth_property(key, g, jit_cache):
         np.testing.assert_allclose(_np(r["Ps"])[b], ref["Ps"], rtol=0, atol=tol, err_msg=what + " Ps")
     if N + K > 16 and N <= 32:
         # the GPU tier's engines start with the split-layout wide filter forced (tests/conftest.py); what a batch this small
-        # gets by DEFAULT is one state per lane (filter_kernel<N,K,64>): the same sweep through it (round-4 advice)
+        # gets by DEFAULT is one state per lane (filter_wave_kernel<N,K>): the same sweep through it (round-4 advice)
         kf.set_variant("wide_filter", "auto")
         assert kf.resolved_wide_filter(B) == "lane_per_state"
         r2 = kf.filter_smooth(g["phi"], g["q"], x0=g["x0"], P0=g["P0"])

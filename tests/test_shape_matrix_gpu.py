@@ -338,3 +338,76 @@ def test_generic_kernel_family(key, g, jit_cache):
         np.testing.assert_allclose(_np(p["sim_vars"])[b], np.maximum(np.einsum("jn,tnm,jm->tj", ref["Z"], ref["Ps"], ref["Z"]), 0.0),
                                    rtol=0, atol=2 * tol, err_msg=what + " sim_vars")
     kf.close()
+
+
+# ------------------------------------------------------------------- filter_wave_kernel: the forms no other test launches
+# The one-model-per-wavefront filter (mk_kernels.hip: filter_wave_kernel<N, K, OUT, BOOK, SYM>) is launched by the tests above
+# and by tests/test_innovations_gpu.py (OUT 0 with BOOK) and tests/test_status_gpu.py (OUT 2) in every form but three: the
+# filtered packed-symmetric record alone (OUT 3, SYM) and the two tapes with per-step sigmas / detfs booked (OUT 4, BOOK).
+WAVE_FORMS = {
+    "filtered_record_sym": (13, 4),    # n = 17, the narrowest wide shape; simulate_smoothed of a packed_sym engine
+    "tape_booked": (33, 4),            # N > 32: the tape's writer; simulate_smoothed with dense sigmas / detfs attached
+    "state_tape_booked": (33, 4),      # ... and smooth_state_variances over the STATE tape
+}
+
+
+def _wave_group(N, K):
+    """B = 3: one surplus wavefront in the 4-model workgroup (the inst > B - 1 clamp).  T = 18: one tile edge and the row clamp
+    of the second tile.  30 % of the cells missing (hard_models' "iid") and one step fully empty, another one per model, so
+    that the compressed index falls behind t (the scattered pad store).  No observation variances: the STATE tape serves R = 0."""
+    B, T = 3, 18
+    rng = np.random.default_rng([N, K, T, B])
+    g = dict(obs=np.empty((B, T, N)), phi=np.empty((B, N + K)), q=np.empty((B, N + K)), loadings=np.empty((B, N, K)),
+             patterns=["iid + empty step %d" % (3 + 5 * b) for b in range(B)], obsvar=None, x0=None, P0=None)
+    for b in range(B):
+        g["obs"][b], g["phi"][b], g["q"][b], g["loadings"][b] = hard_models.draw_model(rng, N, K, T, "iid")
+        g["obs"][b, 3 + 5 * b] = np.nan
+        assert np.isfinite(g["obs"][b, -1]).any() and 0.2 < np.isnan(g["obs"][b]).mean() < 0.45
+    return g
+
+
+@pytest.mark.parametrize("layout", ["model_major", "time_major"])
+@pytest.mark.parametrize("form", sorted(WAVE_FORMS))
+def test_wave_filter_remaining_forms(form, layout, jit_cache):
+    N, K = WAVE_FORMS[form]
+    n, B, T = N + K, 3, 18
+    g = _wave_group(N, K)
+    refs = _refs((N, K, T, B), g, "wave forms")
+    kf = _engine(g, layout, packed_sym=(form == "filtered_record_sym"))
+    kf.set_variant("wide_filter", "lane_per_state")
+    if form == "filtered_record_sym":
+        assert not kf.tape_path()
+        r = _run(kf, "simulate_smoothed", g)
+        assert "_tape" not in r and r["Pf"].shape == (B, T, n * (n + 1) // 2)
+    else:
+        assert kf.tape_path() and kf.state_tape_path()
+        bufs = kf.alloc_projection(B) if form == "tape_booked" else kf.alloc_state_variances(B)
+        bufs["sigmas"], bufs["detfs"] = kf._empty_bt(B, T), kf._empty_bt(B, T)
+        r = _run(kf, "simulate_smoothed" if form == "tape_booked" else "smooth_state_variances", g, buffers=bufs)
+        assert r["_tape"]
+    assert not int(np.bitwise_or.reduce(_np(r["status"])))
+    sig, det = _np(r["sigmas"]), _np(r["detfs"])
+    for b, ref in enumerate(refs):
+        w = "%s %s: model %d (%s)" % (form, layout, b, g["patterns"][b])
+        sc = ref["sigmacount"]
+        assert sc == T - 1, w
+        assert abs(_np(r["mle"])[b] - ref["mle"]) <= hard_models.mle_tolerance(g, b, ref), w
+        atol_sig, atol_mom = hard_models.filter_tolerances(g, b, ref)
+        assert int(_np(r["sigmacount"])[b]) == sc, w
+        np.testing.assert_allclose(sig[b, :sc], ref["sigmas"][:sc], rtol=1e-9, atol=atol_sig, err_msg=w)
+        np.testing.assert_allclose(det[b, :sc], ref["detfs"][:sc], rtol=0, atol=1e-10 + 1e-15 / float(g["q"][b].min()), err_msg=w)
+        assert not sig[b, sc:].any() and not det[b, sc:].any(), w
+        tol = hard_models.smoother_tolerance(g, b, ref)
+        if form == "filtered_record_sym":
+            np.testing.assert_allclose(_np(r["F"])[b], ref["F"], rtol=0, atol=atol_mom, err_msg=w + " F")
+            np.testing.assert_allclose(_np(kf.unpack_sym(r["Pf"]))[b], ref["Pf"], rtol=0, atol=atol_mom, err_msg=w + " Pf")
+        if form == "state_tape_booked":
+            np.testing.assert_allclose(_np(r["S"])[b], ref["S"], rtol=0, atol=tol, err_msg=w + " state means")
+            np.testing.assert_allclose(_np(r["var"])[b], np.diagonal(ref["Ps"], axis1=1, axis2=2), rtol=0, atol=tol,
+                                       err_msg=w + " state variances")
+        else:
+            Z = ref["Z"]
+            np.testing.assert_allclose(_np(r["sim_means"])[b], ref["S"] @ Z.T, rtol=0, atol=2 * tol, err_msg=w + " sim_means")
+            np.testing.assert_allclose(_np(r["sim_vars"])[b], np.maximum(np.einsum("jn,tnm,jm->tj", Z, ref["Ps"], Z), 0.0),
+                                       rtol=0, atol=2 * tol, err_msg=w + " sim_vars")
+    kf.close()

@@ -2,7 +2,7 @@
 chosen for the structure the kernels have along time, not for convenience.
 
 What the kernels tile or pipeline along t (restated below; tests/test_time_axis.py holds each constant to the source text):
-  TS = 16      observation tiles through LDS: filter_kernel (mk_kernels.hip), filter_split_kernel and filter_obs_kernel
+  TS = 16      observation tiles through LDS: filter_kernel and filter_wave_kernel (mk_kernels.hip), filter_split_kernel and filter_obs_kernel
                (mk_split.hip).  A tile is loaded one tile ahead with rows clamped to T - 1; the last step of a tile re-reads its
                own row for ``ynext`` and the outer loop supplies the next tile's first row
   PASS = 256   observed_steps_kernel lists the observed steps 256 time steps per pass (four wavefronts' ballots and a prefix)
@@ -44,7 +44,7 @@ PASS = 256   # time steps per pass of observed_steps_kernel
 
 # (what, file, the source line -- matched textually, a comment after it ignored --, how often the file holds it)
 SOURCE = (
-    ("TS: filter_kernel", "mk_kernels.hip", "constexpr int TS = %d;" % TS, 1),
+    ("TS: filter_kernel and filter_wave_kernel", "mk_kernels.hip", "constexpr int TS = %d;" % TS, 2),
     ("TS: filter_split_kernel and filter_obs_kernel", "mk_split.hip", "constexpr int TS = %d;" % TS, 2),
     ("TSP: loglik_sparse_kernel", "mk_kernels.hip", "constexpr int TSP = %d;" % TSP, 1),
     ("PASS: observed_steps_kernel", "mk_kernels.hip", "for (long t0 = 0; t0 < T; t0 += %d) {" % PASS, 1),
