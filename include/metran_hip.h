@@ -551,6 +551,51 @@ MK_API int64_t mk_ensemble_max_draws(void);
 MK_API int mk_ensemble_summary(mk_context *ctx, int64_t S, int64_t cells, const double *d_values /* [S,cells] */, int64_t nprobs,
                                const double *probs /* HOST array, nprobs <= 16 */, double *d_summary /* [cells, 5 + nprobs] */);
 
+/* OBSERVATION WEIGHTS of smoothed series and states (Koopman & Harvey 2003, J. Econ. Dyn. Control 27:1317-1333; statsmodels'
+ * compute_smoothed_state_weights): which observations a smoothed number comes from.  For fixed parameters the smoother is linear
+ * in the data, so for a TARGET (t*, c) -- c = z_j* (what = MK_DRAW_SERIES: series j*, the unscaled projection z_j* x_{t*|T}) or c = e_i
+ * (what = MK_DRAW_STATES: state i) --
+ *     c' x_{t*|T} = sum over the observed cells (t, j) of  w_{t,j} y_{t,j}  +  intercept,
+ * y the filter's standardised value (no scale, no offset).  Model and filter order as in mk_innovations: prediction first
+ * (x <- phi o x, P <- (phi phi') o P + diag q), then the observed series of the step in ascending order, Z = [I | Gamma].
+ *   PER CELL, with P the covariance just before the scalar update of the observed cell (t, j):  d_{t,j} = P z_j',
+ * rf_{t,j} = 1 / f_{t,j}, k_{t,j} = d_{t,j} rf_{t,j};  d = 0 and rf = 0 at a cell that is not observed, which then drops out of
+ * what follows arithmetically.
+ *   FORWARD from t*:  p = P_{t*|t*-1} c (the predicted covariance of step t*: from the filtered record of step t* - 1, from d_P0 / I
+ * for t* = 0);  for t = t* .. T-1: p <- phi o p if t > t*, then for j ascending  g_{t,j} = (z_j p) rf_{t,j},  p <- p - d_{t,j} g_{t,j};
+ * g = 0 at every cell before step t*.
+ *   BACKWARD over the whole record:  h = 0;  for t = T-1 .. 0: for j descending  w_{t,j} = g_{t,j} + (h k_{t,j}),  h <- h - w_{t,j} z_j';
+ * after the cells of step t, h <- h + c if t = t*; then h <- phi o h.  At the end intercept = h x0 (0 when d_x0 is NULL).
+ *   d_weights [B,M,T,N] (model-major whatever time_major says) holds w, in units of (target per unit of the standardised
+ * observation), NaN at every cell that is not observed; d_intercept [B,M] (may be NULL) the intercept.  Instance i uses the M
+ * targets of record i % n_records, d_targets [n_records,M,2] = (step, column) as 64-bit integers.  A target whose step is outside
+ * [0, T) or whose column is outside [0, N) (series) / [0, N + K) (states) gets an all-NaN row and a NaN intercept, and nothing is
+ * read back on the host; a negative step marks an unused slot.  For R = 0 the smoothed projection of an observed cell is the
+ * observation: its own weight is 1 and all others are 0, up to rounding.
+ *   Launches: the recording forward pass of mk_loglik_grad into d_work -- n_instances * T * mk_weights_work_stride(N, K) doubles:
+ * the filtered full-square records packed at its head (mk_record_stride(N + K) doubles each, addressed by time_major, as in
+ * mk_forecast), the GAIN TAPE behind them: per (instance, step, series) one slot [ d (N + K) | rf | pad ] of (N + K + 3) & ~1 doubles,
+ * cell (b, t, j) at ((b, t) block * N + j) slots, the blocks addressed by time_major like the records -- then one asynchronous clear
+ * of the tape, innov_step_kernel (which re-forms d and rf of every scalar update from the records, in parallel over time, and
+ * stores them; its v / f / forecast outputs are not asked for) and weights_walk_kernel (one target per lane group, lane = state;
+ * one forward and one backward vector walk, O(N + K) per cell), all on the context's stream, the three timed in the smoother slot
+ * of mk_last_kernel_ms / mk_kernel_ms_totals.  Every sum is a fixed tree over the lanes: a target's weights are bit-identical
+ * whatever batch, n_targets or neighbouring targets it runs with.  prob->warmup is ignored; d_status (may be NULL) receives the
+ * filter's MK_FLAG_* bits -- the outputs of an instance with MK_FLAG_NONPOSITIVE_F are not meaningful.
+ *   Served: every supported shape with N + K <= 64, under either kernel family; mk_weights_work_stride returns 0 otherwise and
+ * mk_observation_weights fails with MK_ERR_SHAPE.  MK_ERR_INVALID (no launch): a missing d_work, d_targets or d_weights,
+ * n_targets < 1, a `what` that is neither MK_DRAW_SERIES nor MK_DRAW_STATES, a buffer larger than the allocation it points into. */
+typedef struct mk_weights_request {
+    int64_t n_targets;            /* M per record, >= 1 */
+    int what;                     /* MK_DRAW_SERIES: c = z_j;  MK_DRAW_STATES: c = e_i */
+    const int64_t *d_targets;     /* [n_records, M, 2] = (step, column); instance i uses the targets of record i % n_records */
+    double *d_weights;            /* [B, M, T, N], model-major whatever time_major says */
+    double *d_intercept;          /* [B, M] or NULL */
+} mk_weights_request;
+MK_API int64_t mk_weights_work_stride(int64_t N, int64_t K);
+MK_API int mk_observation_weights(mk_context *ctx, const mk_problem *prob, double *d_work, int time_major,
+                                  const mk_weights_request *req, uint32_t *d_status);
+
 /* kalmansmoother for B instances (kalmanfilter.py:403-476).  Reads out->d_F and out->d_Pf
  * (as written by mk_filter); predicted moments are recomputed from them (Phi diagonal), so
  * d_Xp/d_Pp are not read.  Writes d_S, d_Ps (either may be NULL), d_status.  d_status is OVERWRITTEN (cleared on the context's

@@ -8,7 +8,7 @@ import ctypes
 import os
 from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
 
-__all__ = ["MetranHipError", "lib", "library_path", "Problem", "Outputs", "ForecastRequest", "check", "API"]
+__all__ = ["MetranHipError", "lib", "library_path", "Problem", "Outputs", "ForecastRequest", "WeightsRequest", "check", "API"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIBNAME = "libmetran_hip.so"
@@ -87,6 +87,18 @@ class ForecastRequest(Structure):
     ]
 
 
+class WeightsRequest(Structure):
+    """``mk_weights_request`` (include/metran_hip.h)."""
+
+    _fields_ = [
+        ("n_targets", c_int64),
+        ("what", c_int),
+        ("d_targets", c_void_p),
+        ("d_weights", c_void_p),
+        ("d_intercept", c_void_p),
+    ]
+
+
 # name -> (restype, argtypes); this table is what tests check against the header.
 API = {
     "mk_abi_version": (c_int, []),
@@ -156,6 +168,8 @@ API = {
     "mk_forecast_max_horizon": (c_int64, []),
     "mk_forecast_work_stride": (c_int64, [c_int64, c_int64]),
     "mk_forecast": (c_int, [c_void_p, POINTER(Problem), c_void_p, c_int, POINTER(ForecastRequest), c_void_p]),
+    "mk_weights_work_stride": (c_int64, [c_int64, c_int64]),
+    "mk_observation_weights": (c_int, [c_void_p, POINTER(Problem), c_void_p, c_int, POINTER(WeightsRequest), c_void_p]),
     "mk_draw_perturb": (c_int, [c_void_p, POINTER(Problem), c_uint64, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p,
                                 c_void_p]),
     "mk_draw_combine": (c_int, [c_void_p, POINTER(Problem), c_int64, c_int, c_int, c_void_p, c_void_p]),

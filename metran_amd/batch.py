@@ -13,6 +13,8 @@ number comes from the HIP kernels:
     disturbances             ->  smoothed state disturbances and auxiliary residuals (get_auxiliary_residuals, screen_breaks)
     forecast                 ->  multi-step-ahead forecasts and forecast skill by horizon (get_forecast, get_prediction_at,
                                  forecast_skill)
+    observation_weights      ->  which observations a smoothed value comes from (get_observation_weights, get_state_weights,
+                                 get_weight_shares)
     draw_smoothed            ->  posterior draws of series and states (get_simulation_draws, get_state_draws)
     draw_window_statistics   ->  window statistics of the draws, reduced on the device (get_window_statistics)
 
@@ -418,6 +420,129 @@ class MetranBatch:
                                "logscore": -0.5 * (np.log(2.0 * np.pi) + flat[:, 4] / m + msse), "coverage": flat[:, 5] / m,
                                "nominal": np.where(np.isnan(m), np.nan, float(coverage)), "skill": 1.0 - mse / var}, index=index)
         return frame
+
+    # ------------------------------------------------------------------ observation weights (which data a number comes from)
+    def _target_steps(self, r, times):
+        """``times`` of the weight accessors as integer steps of model ``r``: timestamps on the model's index or integer steps,
+        one or a list."""
+        from pandas import Timestamp
+
+        index = self.batch.index[r]
+        if isinstance(times, (str, Timestamp, np.datetime64, int, np.integer)) or not hasattr(times, "__iter__"):
+            times = [times]
+        steps = []
+        for t in times:
+            if isinstance(t, (int, np.integer)):
+                if not 0 <= int(t) < len(index):
+                    raise IndexError("step %d is outside the model's %d steps" % (int(t), len(index)))
+                steps.append(int(t))
+            else:
+                pos = index.get_indexer([Timestamp(t)])[0]
+                if pos < 0:
+                    raise KeyError("%s is not on the index of model %d" % (t, r))
+                steps.append(int(pos))
+        if not steps:
+            raise ValueError("times must name at least one step")
+        return steps
+
+    def _weights(self, r, column, steps, what, alpha):
+        """``BatchedKalman.observation_weights`` for the targets (step, column) of model ``r``, run on a sub-engine that holds
+        that model alone (``BatchedKalman.subset``: the walks cost one pass over a record per target, the other models' records
+        are not touched): ``(w [M,T,N], intercept [M])`` on the device, in the filter's units; the cached kind "weights", one
+        result per request of the parameter set it was computed with."""
+        import torch
+
+        from .kalmanfilter import check_status
+
+        a = self._alpha(alpha)
+        request = (int(r), int(column), tuple(steps), what)
+        hit = self._cache.get("weights")
+        if hit is None or hit[0].shape != a.shape or not bool(torch.equal(hit[0], a)):
+            hit = self._cache["weights"] = (a.clone(), {})
+        if request not in hit[1]:
+            phi, q = self.kf.params_from_alpha(a, dt=self.dt)
+            targets = np.stack([np.asarray(steps, dtype=np.int64), np.full(len(steps), column, dtype=np.int64)], axis=1)
+            out = self.kf.subset([r]).observation_weights(phi[r:r + 1], q[r:r + 1], targets, what=what)
+            check_status(out["status"], "MetranBatch(weights)")
+            hit[1][request] = (out["weights"][0], out["intercept"][0])   # the workspace (records and gain tape) is not kept
+        return hit[1][request]
+
+    def _weight_frames(self, r, steps, w, intercept):
+        from pandas import DataFrame
+
+        L = int(self.batch.lengths[r])
+        w, intercept = w.cpu().numpy(), intercept.cpu().numpy()
+        frames = {}
+        for m, s in enumerate(steps):
+            frame = DataFrame(w[m, :L], index=self.batch.index[r], columns=list(self.batch.names[r]))
+            frame.attrs["intercept"] = float(intercept[m])
+            frames[self.batch.index[r][s]] = frame
+        return frames
+
+    def get_observation_weights(self, r, name, times, alpha=None, standardized=False):
+        """Which observations the smoothed value of series ``name`` of model ``r`` comes from (``get_simulation``'s mean, e.g. a
+        gap-filled value): for fixed parameters the smoother is linear in the data, so that mean is a weighted sum of the model's
+        observations (Koopman & Harvey 2003; ``BatchedKalman.observation_weights``).  ``times``: timestamps on the model's index
+        or integer steps, one or a list.  Returns a dict timestamp -> DataFrame (index = the model's time index, columns = its
+        series) of the weights, NaN where a series is not observed; the part that comes from the initial state is
+        ``frame.attrs["intercept"]`` (0 for the default initial state).  Original units (the default): with y the observations,
+        ``sum_i,t w (y_i - mean_i) + mean_name + intercept`` is ``get_simulation``'s mean at that time -- the weight of series i is
+        ``w std_name / std_i`` of the standardised one.  ``standardized=True``: the units the filter runs in,
+        ``sum w y_standardised + intercept`` is the standardised mean."""
+        j = self._series(r, name)
+        steps = self._target_steps(r, times)
+        w, intercept = self._weights(r, j, steps, "series", alpha)
+        if not standardized:
+            w = w * (self._std[r, j] / self._std[r])[None, None, :]
+            intercept = intercept * self._std[r, j]
+        return self._weight_frames(r, steps, w, intercept)
+
+    def get_state_weights(self, r, i, times, alpha=None):
+        """``get_observation_weights`` for state ``i`` of model ``r`` (``get_state``'s mean), in the filter's units:
+        ``sum w y_standardised + intercept`` is the smoothed state."""
+        if i < 0 or i >= self.N + self.K:
+            raise IndexError("Value of i must be >=0 and <%d" % (self.N + self.K))
+        steps = self._target_steps(r, times)
+        w, intercept = self._weights(r, int(i), steps, "states", alpha)
+        return self._weight_frames(r, steps, w, intercept)
+
+    def get_weight_shares(self, r, name, times, alpha=None, mass=0.9):
+        """What the smoothed value of series ``name`` of model ``r`` at ``times`` leans on, one row per (time, source series):
+        ``sum_w`` (the sum of the series' weights over time), ``share`` (``sum_t |w|`` of the series over ``sum_t,i |w|`` of all,
+        in standardised units: the shares of a time add up to 1) and ``first`` / ``last``, the time stamps of the SHORTEST run of
+        steps that contains the target's step and holds ``mass`` (90 %) of the series' ``sum_t |w|`` -- the earliest such run
+        when several are equally short; NaT for a series without weight (never observed).  Reduced on the device; only the
+        table crosses to the host."""
+        import torch
+        from pandas import DataFrame, MultiIndex, NaT
+
+        j = self._series(r, name)
+        steps = self._target_steps(r, times)
+        w, _ = self._weights(r, j, steps, "series", alpha)          # [M,T,N], standardised units
+        M, T, N = (int(s) for s in w.shape)
+        w0 = torch.nan_to_num(w, nan=0.0)
+        aw = w0.abs().permute(0, 2, 1).reshape(M * N, T).contiguous()   # one row per (target, series)
+        tot = aw.sum(1)
+        csum = torch.cumsum(aw, 1)                                  # inclusive prefix sums, non-decreasing
+        before = csum - aw                                          # the mass before step a
+        # for every start a the first end b whose run holds the mass; the run must contain the target's step
+        need = before + float(mass) * tot[:, None]
+        need = torch.minimum(need, tot[:, None])                    # rounding must not ask for more than there is
+        end = torch.searchsorted(csum, need, right=False)
+        tstar = torch.as_tensor(steps, device=w.device).repeat_interleave(N)[:, None]
+        end = torch.maximum(end, tstar)
+        start = torch.arange(T, device=w.device)[None, :]
+        ok = (start <= tstar) & (end < T)
+        length = torch.where(ok, end - start, torch.full_like(end, 2 * T))
+        first = torch.argmin(length, 1)
+        last = end.gather(1, first[:, None])[:, 0]
+        table = torch.stack([w0.sum(1).reshape(-1), tot / tot.reshape(M, N).sum(1).repeat_interleave(N), first.to(w.dtype), last.to(w.dtype),
+                             tot], 1).cpu().numpy()
+        index = self.batch.index[r]
+        rows = [(index[s], nm) for s in steps for nm in self.batch.names[r]]
+        stamp = lambda v, k: index[int(v[k])] if v[4] > 0 else NaT  # noqa: E731
+        return DataFrame({"sum_w": table[:, 0], "share": table[:, 1], "first": [stamp(v, 2) for v in table], "last": [stamp(v, 3) for v in table]},
+                         index=MultiIndex.from_tuples(rows, names=["time", "series"]))
 
     # ------------------------------------------------------------------ state disturbances (break detection)
     def get_state_disturbances(self, alpha=None):

@@ -20,6 +20,8 @@ struct InnovArgs {
     const double *F;         // filtered record array written by the recording forward pass
     double *v, *f;           // innovation and its variance of every observed cell (NaN elsewhere), or NULL
     double *pred_mean, *pred_var; // marginal one-step-ahead forecast of every series, or NULL
+    double *gain;            // gain tape (weights_kernels.h), or NULL: per (b, t, j) one slot [ d = P z_j' (n) | 1/f | pad ] of gs doubles
+    long gs;                 // at ((b*bs + t*ts)*N + j)*gs, written for the observed cells only (the caller clears the tape)
 };
 
 struct InnovStatsArgs {

@@ -14,7 +14,9 @@
 //                     all zero (a run-time uniform branch per block around compile-time register indices; a zero inside a kept
 //                     block adds exactly nothing): the same multiply-adds in the same order as the filter kernels', so v and f
 //                     are the filter's own numbers.  No cross-lane instruction chains: the pairs are
-//                     independent and occupancy hides the latencies.
+//                     independent and occupancy hides the latencies.  With InnovArgs.gain set the kernel also stores d and
+//                     1 / f of every scalar update -- lane r its d_r -- into the cell's slot of the gain tape that
+//                     weights_kernels.hip walks; v, f and the forecasts are the same numbers with or without it.
 // innov_stats_kernel  One wavefront per (instance, series): time in tiles of kInnovTile steps, a lane per step.  TWO passes over v / f:
 //                     the mean first, then the lagged products of the centred values -- the second pass RE-READS v and f (a series
 //                     is 16 T bytes; the tile's cells were just read and sit in L2) instead of keeping the series in LDS, whose
@@ -165,7 +167,7 @@ __global__ void __launch_bounds__(G == 16 ? 256 : 64) innov_step_kernel(InnovArg
             if (a.pred_var) a.pred_var[orow] = scaled_var(pv, sc);
         }
     }
-    if (!(a.v || a.f)) return;
+    if (!(a.v || a.f || a.gain)) return;
 
     // ---- sequential scalar updates (:341-378), ascending series order over the observed series
     double vown = nan, fown = nan;
@@ -201,6 +203,11 @@ __global__ void __launch_bounds__(G == 16 ? 256 : 64) innov_step_kernel(InnovArg
             }
         }
         const double rf = rcp_nr(f), kr = d * rf;
+        if (a.gain && live) { // the slot of cell (t, j): lane r its d_r, the first lane 1/f
+            double *slot = a.gain + ((b * a.bs + t * a.ts) * N + j) * a.gs;
+            if (act) slot[lane] = d;
+            if (lane == 0) slot[n] = rf;
+        }
 #pragma unroll
         for (int c0 = 0; c0 < W; c0 += 4) { // P -= k k' f (:368-372)
             if (c0 < n) {

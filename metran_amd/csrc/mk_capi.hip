@@ -19,6 +19,7 @@
 #include "mk_generic.h"
 #include "mk_internal.h"
 #include "mk_lbfgs.h"
+#include "weights_kernels.h"
 
 struct mk_context {
     int device;
@@ -187,7 +188,7 @@ hipError_t dispatch_smoother(mk_context *ctx, int N, int K, const mk::SmootherAr
 }
 } // namespace
 
-// ---- what the kernels' argument blocks share, filled from mk_problem.  FilterArgs, AdjointArgs, InnovArgs, ForecastArgs and DrawArgs
+// ---- what the kernels' argument blocks share, filled from mk_problem.  FilterArgs, AdjointArgs, InnovArgs, ForecastArgs, WeightsArgs and DrawArgs
 // spell these fields alike (SparseArgs and SmootherArgs a part of them); the structs themselves stay apart, because a kernel that
 // takes its block by value is compiled against that block's layout ----
 template <class Args>
@@ -1510,6 +1511,77 @@ MK_API int mk_forecast(mk_context *ctx, const mk_problem *p, double *d_work, int
     MK_HIP(timing_start(ctx, 1));
     if (fan || track) MK_HIP(mk::launch_forecast_path(a, ctx->stream));
     if (skill) MK_HIP(mk::launch_forecast_skill(a, ctx->stream));
+    MK_HIP(timing_stop(ctx, 1)); // reported in the smoother slot of mk_last_kernel_ms / mk_kernel_ms_totals
+    return MK_OK;
+}
+
+// ---- observation weights of smoothed series and states (weights_kernels.hip) ----
+MK_API int64_t mk_weights_work_stride(int64_t N, int64_t K)
+{
+    if (N < 1 || K < 1 || N + K > mk::weights_max_states || !mk_shape_supported(N, K)) return 0;
+    return mk::record_stride((int)(N + K)) + N * mk::weights_slot_stride(N + K);
+}
+
+MK_API int mk_observation_weights(mk_context *ctx, const mk_problem *p, double *d_work, int time_major, const mk_weights_request *req,
+                                  uint32_t *d_status)
+{
+    MK_CTX(ctx);
+    // refused first: every other shape that mk_weights_work_stride does not serve is one check_problem refuses
+    if (p && p->N >= 1 && p->K >= 1 && p->N + p->K > mk::weights_max_states)
+        return too_many_states("mk_observation_weights", p, mk::weights_max_states);
+    if (int rc = check_problem(p)) return rc;
+    if (!req) return fail(MK_ERR_INVALID, "mk_observation_weights: null mk_weights_request");
+    if (!d_work) return fail(MK_ERR_INVALID, "mk_observation_weights: d_work is required");
+    if (!req->d_targets || !req->d_weights) return fail(MK_ERR_INVALID, "mk_observation_weights: d_targets and d_weights are required");
+    if (req->n_targets < 1) return fail(MK_ERR_INVALID, "mk_observation_weights: need n_targets >= 1 (got %lld)", (long long)req->n_targets);
+    if (req->what != MK_DRAW_SERIES && req->what != MK_DRAW_STATES)
+        return fail(MK_ERR_INVALID, "mk_observation_weights: what must be MK_DRAW_SERIES or MK_DRAW_STATES (got %d)", req->what);
+    if (!p->d_obs || !p->d_loadings) return fail(MK_ERR_INVALID, "d_obs and d_loadings are required");
+    const int64_t ws = mk_weights_work_stride(p->N, p->K);
+    if (!ws) return too_many_states("mk_observation_weights", p, mk::weights_max_states);
+    const int64_t B = p->n_instances, M = req->n_targets, n = p->N + p->K;
+    const int64_t rs = mk::record_stride((int)n), gs = mk::weights_slot_stride(n);
+    static_assert(sizeof(int64_t) == sizeof(double), "buffers_fit counts 8-byte words");
+    const device_buffer bufs[4] = {{d_work, B * p->T * ws, "d_work (n_instances * T * mk_weights_work_stride(N, K) doubles)"},
+                                   {req->d_targets, p->n_records * M * 2, "d_targets (n_records * n_targets * 2 64-bit integers)"},
+                                   {req->d_weights, B * M * p->T * p->N, "d_weights (n_instances * n_targets * T * N doubles)"},
+                                   {req->d_intercept, B * M, "d_intercept (n_instances * n_targets doubles)"}};
+    if (int rc = buffers_fit("mk_observation_weights", bufs, 4)) return rc;
+    // the records are packed at the head of d_work; the gain tape lives behind them
+    if (int rc = record_pass(ctx, p, d_work, rs, time_major, d_status)) return rc;
+    double *tape = d_work + B * p->T * rs;
+    mk::InnovArgs g;
+    memset(&g, 0, sizeof(g));
+    fill_model(g, p);
+    fill_initial(g, p);
+    fill_layout(g, time_major, B, p->T);
+    g.N = (int)p->N;
+    g.K = (int)p->K;
+    g.rs = rs;
+    g.F = d_work;
+    g.gain = tape;
+    g.gs = gs;
+    mk::WeightsArgs a;
+    memset(&a, 0, sizeof(a));
+    fill_model(a, p);
+    fill_initial(a, p);
+    fill_layout(a, time_major, B, p->T);
+    a.N = (int)p->N;
+    a.K = (int)p->K;
+    a.M = M;
+    a.states = req->what == MK_DRAW_STATES ? 1 : 0;
+    a.rs = rs;
+    a.gs = gs;
+    a.F = d_work;
+    a.gain = tape;
+    a.targets = req->d_targets;
+    a.weights = req->d_weights;
+    a.intercept = req->d_intercept;
+    MK_HIP(timing_start(ctx, 1));
+    // a cell that is not observed keeps an all-zero slot: innov_step_kernel writes the observed ones only
+    MK_HIP(hipMemsetAsync(tape, 0, sizeof(double) * (size_t)(B * p->T * p->N * gs), ctx->stream));
+    MK_HIP(mk::launch_innov_step(g, ctx->stream));
+    MK_HIP(mk::launch_weights_walk(a, ctx->stream));
     MK_HIP(timing_stop(ctx, 1)); // reported in the smoother slot of mk_last_kernel_ms / mk_kernel_ms_totals
     return MK_OK;
 }

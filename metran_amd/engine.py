@@ -14,7 +14,7 @@ import logging
 import numpy as np
 
 from . import _lib
-from ._lib import ForecastRequest, MetranHipError, Outputs, Problem, check
+from ._lib import ForecastRequest, MetranHipError, Outputs, Problem, WeightsRequest, check
 
 logger = logging.getLogger(__name__)
 
@@ -707,9 +707,9 @@ class BatchedKalman:
         return res
 
     # ------------------------------------------------------------------ the record readers: one scaffold
-    # loo_predict, disturbances, innovations and forecast run the recording forward pass into a workspace ("_work") and one kernel
+    # loo_predict, disturbances, innovations, forecast and observation_weights run the recording forward pass into a workspace ("_work") and one kernel
     # that reads its filtered records.  NOTE: loo_supported() and disturbances_supported() are methods, innovations_supported and
-    # forecast_supported properties -- an inconsistency of the public API that is kept.
+    # forecast_supported / observation_weights_supported properties -- an inconsistency of the public API that is kept.
     def _reader_stride(self, fn, specialised_only, refusal=None):
         """Doubles per (instance, step) of a record reader's workspace, the C ABI's ``fn(N, K)``; where the shape is not served
         0, or with ``refusal`` (a text with places for N and K) a MetranHipError."""
@@ -967,6 +967,65 @@ class BatchedKalman:
         check(self._L.mk_forecast(self._ctx, ctypes.byref(prob), self._p(res["_work"]), 1 if self.time_major else 0, ctypes.byref(req),
                                   self._p(res["status"])))
         self._mask_bad_instances(res, [key for key in shapes if key != "_work"])
+        return res
+
+    # ------------------------------------------------------------------ observation weights of smoothed series and states
+    @property
+    def observation_weights_supported(self):
+        """True when ``observation_weights`` serves this engine's shape (C ABI ``mk_weights_work_stride`` > 0): N + K <= 64,
+        specialised or size-generic kernels alike."""
+        return self._reader_stride(self._L.mk_weights_work_stride, False) > 0
+
+    def _weights_stride(self):
+        return self._reader_stride(self._L.mk_weights_work_stride, False,
+                                   "observation weights serve shapes with N + K <= 64; (N=%s, K=%s) is not one")
+
+    def _weights_shapes(self, B, M):
+        """name -> (logical shape, follows the engine's layout) of the buffers of ``observation_weights``."""
+        shapes = self._bt_shapes(B, _work=self._weights_stride())
+        shapes["weights"] = ((B, M, self.T, self.N), False)
+        shapes["intercept"] = ((B, M), False)
+        return shapes
+
+    def alloc_observation_weights(self, B, M):
+        """Buffers of ``observation_weights`` for B instances and M targets per record (the forward pass's workspace with the
+        gain tape + the two outputs), for callers that run it repeatedly (pass them back as ``buffers=``)."""
+        M = int(M)
+        if M < 1:
+            raise ValueError("M must be >= 1")
+        return self._reader_buffers(None, self._weights_shapes(B, M), "alloc_observation_weights", sep=", ")
+
+    def observation_weights(self, phi, q, targets, what="series", x0=None, P0=None, buffers=None):
+        """OBSERVATION WEIGHTS of smoothed series or states for B instances (C ABI ``mk_observation_weights``; Koopman & Harvey
+        2003): for fixed parameters the smoother is linear in the data, so the projected smoothed mean at a target is
+        ``sum w * y + intercept`` over the observed cells of the record, ``y`` the standardised observations the filter runs on.
+        ``targets``: ``[R,M,2]`` integers ``(step, column)`` (or ``[M,2]``, shared by the records) -- column = series j
+        (``what="series"``: the unscaled projection ``z_j x_{t|T}``) or state i (``what="states"``); instance b uses the targets of
+        record ``b % R``.  Returns a dict with ``weights [B,M,T,N]`` (NaN at every cell that is not observed), ``intercept [B,M]``
+        (the part that comes from ``x0``) and ``status`` (the filter's MK_FLAG_* bits); the rows of an instance whose status
+        carries ``FLAG_NONPOSITIVE_F`` are NaN.  A target whose step is outside ``[0, T)`` or whose column is out of range has an
+        all-NaN row (a negative step marks an unused slot).  Four launches (the recording forward pass, a clear, the gain writer,
+        one walk per target); a target's weights do not depend on the batch or on the other targets, bit for bit."""
+        torch = _torch()
+        if what not in ("series", "states"):
+            raise ValueError("what must be 'series' or 'states'")
+        self._weights_stride()
+        tg = torch.as_tensor(targets, dtype=torch.int64)
+        if tg.ndim == 2:
+            tg = tg[None].expand(self.R, -1, -1)
+        if tg.ndim != 3 or tg.shape[0] != self.R or tg.shape[1] < 1 or tg.shape[2] != 2:
+            raise ValueError("targets must be [%d,M,2] (or [M,2]) integers (step, column), M >= 1" % self.R)
+        tg = tg.to(self.device).contiguous()
+        M = int(tg.shape[1])
+        prob, keep, B = self._problem(phi, q, 0, x0, P0)
+        res = self._reader_buffers(buffers, self._weights_shapes(B, M), "alloc_observation_weights", sep=", ")
+        req = WeightsRequest()
+        req.n_targets, req.what = M, 0 if what == "series" else 1   # MK_DRAW_SERIES / MK_DRAW_STATES
+        req.d_targets, req.d_weights, req.d_intercept = tg.data_ptr(), res["weights"].data_ptr(), res["intercept"].data_ptr()
+        self._bind_stream()
+        check(self._L.mk_observation_weights(self._ctx, ctypes.byref(prob), self._p(res["_work"]), 1 if self.time_major else 0,
+                                             ctypes.byref(req), self._p(res["status"])))
+        self._mask_bad_instances(res, ("weights", "intercept"))
         return res
 
     # ------------------------------------------------------------------ posterior draws (simulation smoother)
