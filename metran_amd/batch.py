@@ -1,6 +1,6 @@
 """Many Metran models at once: everything a user of ``metran.Metran`` calls after construction (``get_factors``,
 ``solve``, ``get_mle``, ``get_simulated_means/variances``, ``get_simulation``, ``decompose_simulation``,
-``get_state_means/variances``, ``get_state``, ``mask_observations``; /root/reference/metran/metran.py:199-226,
+``get_state_means/variances``, ``get_state``, ``mask_observations``; metran/metran.py:199-226,
 464-506, 605-989, 991-1045) on top of the batched engine.  The orchestration is Python, as in the reference; every
 number comes from the HIP kernels:
 
@@ -18,19 +18,62 @@ number comes from the HIP kernels:
     draw_smoothed            ->  posterior draws of series and states (get_simulation_draws, get_state_draws)
     draw_window_statistics   ->  window statistics of the draws, reduced on the device (get_window_statistics)
 
-Results of the last filter / smoother run are cached per parameter set, like ``Metran._run_kalman`` does
-(metran.py:963-989): asking for another series, the variances after the means, or the decomposition after the
-simulation does not launch anything.  With ``torch.distributed`` initialised and ``shard=True`` each rank ingests and
-owns a contiguous slice of the models (``distributed.shard_range``); no collective is needed (per-model parameters)
-and ``gather`` concatenates per-model results in rank order.
+Results are cached like ``Metran._run_kalman`` does (metran.py:963-989), by one method (``MetranBatch._run``) over one
+table (``_KINDS``): ``_cache[kind] = (parameter set, {request: kept result})``.  Every kind holds the results of ONE
+parameter set -- different kinds may hold different ones -- and of that result only the keys its accessors read (the table's
+keep-list: never the forward pass's workspace, the records or the tape, which are hundreds of times the outputs), plus what
+the accessors derive from them once (``("simf", standardized)``, ``("decomp", standardized)``).  The kinds with a request
+(``forecast``, ``weights``) keep every request of their parameter set; another parameter set drops them all.  ``solve``,
+``mask_observations`` and ``unmask_observations`` clear the cache.  So asking for another series, the variances after the
+means, or the decomposition after the simulation does not launch anything.  The draws and their window statistics are not
+cached: an ensemble is the size of the thing it summarises.
+
+With ``torch.distributed`` initialised and ``shard=True`` each rank ingests and owns a contiguous slice of the models
+(``distributed.shard_range``); no collective is needed (per-model parameters) and ``gather`` concatenates per-model results
+in rank order.
 """
 import numpy as np
 
 from .calibrate import calibrate_batch
 from .engine import BatchedKalman
 from .ingest import ObservationBatch
+from .kalmanfilter import check_status
 
 __all__ = ["MetranBatch"]
+
+
+def _forecast(mb, phi, q, request):
+    """request = (outputs, horizon, track horizon, first origin, coverage); the fan from every model's last real step
+    (``lengths[r] - 1``: shorter records are padded with empty steps)."""
+    outputs, horizon, track_horizon, t_first, coverage = request
+    return mb.kf.forecast(phi, q, horizon=horizon, outputs=outputs, origins=np.asarray(mb.batch.lengths, dtype=np.int64) - 1,
+                          track_horizon=track_horizon, t_first=t_first, coverage=coverage)
+
+
+def _weights(mb, phi, q, request):
+    """request = (model, column, steps, what), run on a sub-engine that holds that model alone (``BatchedKalman.subset``: the
+    walks cost one pass over a record per target, the other models' records are not touched)."""
+    r, column, steps, what = request
+    targets = np.stack([np.asarray(steps, dtype=np.int64), np.full(len(steps), column, dtype=np.int64)], axis=1)
+    return mb.kf.subset([r]).observation_weights(phi[r:r + 1], q[r:r + 1], targets, what=what)
+
+
+# kind -> (engine call (facade, phi, q, request), whether the scaling is set first, keys of the result that are kept).
+# The scaling is set where the call writes ORIGINAL units: the projection, the leave-one-out predictions, the one- and
+# multi-step-ahead forecasts.  "q" is the q the run was computed for.
+_KINDS = {
+    "project": (lambda mb, phi, q, _: mb.kf.simulate_smoothed(phi, q), True, ("sim_means", "sim_vars")),
+    # state means + variances only (MK_OUT_VAR_ONLY): the smoothed covariances [R,T,n,n] are never written (wide models: the
+    # state tape, BatchedKalman.state_tape_path)
+    "smoother": (lambda mb, phi, q, _: mb.kf.smooth_state_variances(phi, q), False, ("S", "var")),
+    "filter": (lambda mb, phi, q, _: mb.kf.filter(phi, q, outputs=("F", "Pf")), False, ("F", "Pf")),
+    "loo": (lambda mb, phi, q, _: mb.kf.loo_predict(phi, q), True, ("loo_means", "loo_vars")),
+    # v / f in standardised units, pred_mean / pred_var in original units
+    "innov": (lambda mb, phi, q, _: mb.kf.innovations(phi, q), True, ("v", "f", "pred_mean", "pred_var")),
+    "dist": (lambda mb, phi, q, _: mb.kf.disturbances(phi, q), False, ("r", "ninfo", "q")),
+    "forecast": (_forecast, True, ("fan_mean", "fan_var", "track_mean", "track_var", "skill")),
+    "weights": (_weights, False, ("weights", "intercept")),
+}
 
 
 class MetranBatch:
@@ -51,47 +94,58 @@ class MetranBatch:
     def __init__(self, models, factors=None, device=None, tmin=None, tmax=None, min_pairs=20, dt=1.0, maxfactors=None,
                  shard=False):
         models = list(models)
-        self.n_models_total = len(models)
-        self.shard = (0, len(models))
+        total = len(models)
+        span = (0, total)
         if shard:
             from .distributed import shard_range, world
 
             rank, size = world()
-            self.shard = shard_range(len(models), rank, size)
-            models = models[self.shard[0]:self.shard[1]]
+            span = shard_range(total, rank, size)
+            models = models[span[0]:span[1]]
             if factors is not None and np.ndim(factors) == 3:
-                factors = np.asarray(factors)[self.shard[0]:self.shard[1]]
-        self.batch = ObservationBatch(models, tmin=tmin, tmax=tmax, min_pairs=min_pairs)
-        self.kf = BatchedKalman(device, layout="time_major")
-        self.batch.upload(self.kf)  # standardised records + (std, mean) scaling on the device
-        R, T, N = self.batch.shape
-        self.eigval = self.fep = self.nfactors = None
+                factors = np.asarray(factors)[span[0]:span[1]]
+        batch = ObservationBatch(models, tmin=tmin, tmax=tmax, min_pairs=min_pairs)
+        kf = BatchedKalman(device, layout="time_major")
+        batch.upload(kf)  # standardised records + (std, mean) scaling on the device
+        eigval = fep = nfactors = None
         if factors is None:
             from .factoranalysis import FactorAnalysisBatch
 
-            fa = FactorAnalysisBatch(maxfactors=maxfactors, engine=self.kf).solve()
-            self.nfactors = fa.nfactors.cpu().numpy()
-            if (self.nfactors == 0).any():
-                bad = np.nonzero(self.nfactors == 0)[0]
+            fa = FactorAnalysisBatch(maxfactors=maxfactors, engine=kf).solve()
+            nfactors = fa.nfactors.cpu().numpy()
+            if (nfactors == 0).any():
+                bad = np.nonzero(nfactors == 0)[0]
                 # the reference cannot solve such a model either (metran.py:1022-1023: factors is None)
                 raise Exception("No proper common factors could be derived from series of model(s) %s"
-                                % ", ".join(str(int(b) + self.shard[0]) for b in bad))
+                                % ", ".join(str(int(b) + span[0]) for b in bad))
             factors = fa.factors.cpu().numpy()
-            self.eigval = fa.eigval.cpu().numpy()
-            self.fep = fa.fep.cpu().numpy()
+            eigval = fa.eigval.cpu().numpy()
+            fep = fa.fep.cpu().numpy()
         factors = np.asarray(factors, dtype=np.float64)
         if factors.ndim == 2:
-            factors = np.broadcast_to(factors, (R,) + factors.shape).copy()
-        if self.nfactors is None:
-            self.nfactors = np.full(R, factors.shape[2], dtype=np.int64)
-        self.kf.set_loadings(factors)
+            factors = np.broadcast_to(factors, (batch.shape[0],) + factors.shape).copy()
+        kf.set_loadings(factors)
+        self._assemble(batch, kf, kf.scale, kf.offset, factors, nfactors, dt, span, total, eigval, fep)
+
+    def _assemble(self, batch, kf, std, mean, factors, nfactors=None, dt=1.0, shard=None, n_models_total=None, eigval=None, fep=None):
+        """Every attribute of the facade from its parts -- the ingested batch, the engine that holds its standardised records and
+        the loadings ``factors [R,N,K]``, the series' ``std`` / ``mean`` ``[R,N]`` on the engine's device; ``shard`` the span of
+        this rank's models among all ``n_models_total`` (default: all of them) -- what ``__init__`` ends with, and what builds a
+        facade over a stand-in engine where there is no GPU (tests/batch_standin.py)."""
+        self.batch, self.kf = batch, kf
+        self.R, self.T, self.N = batch.shape
+        self.K = int(factors.shape[2])
         self.factors = factors
-        self.R, self.T, self.N, self.K = R, T, N, int(factors.shape[2])
+        self.nfactors = np.full(self.R, self.K, dtype=np.int64) if nfactors is None else nfactors
+        self.eigval, self.fep = eigval, fep
         self.dt = float(dt)
-        self._std, self._mean = self.kf.scale, self.kf.offset
+        self.shard = (0, self.R) if shard is None else shard
+        self.n_models_total = self.R if n_models_total is None else n_models_total
+        self._std, self._mean = std, mean
         self.alpha = None
         self.fit = None
         self._cache = {}
+        return self
 
     # ------------------------------------------------------------------ parameters / objective
     def _alpha(self, alpha):
@@ -101,10 +155,24 @@ class MetranBatch:
             return self.alpha
         return self.kf._dev(alpha, (self.R, self.N + self.K), "alpha")
 
+    def _params(self, alpha, scaling=False):
+        """``(phi, q)`` of the parameter set (None: the default one); ``scaling``: the engine's next call writes original units."""
+        phi, q = self.kf.params_from_alpha(self._alpha(alpha), dt=self.dt)
+        if scaling:
+            self.kf.set_scaling(self._std, self._mean)
+        return phi, q
+
+    def _launch(self, what, alpha, scaling, call):
+        """The way to the engine: the parameters, the scaling, ``call(phi, q)`` and the check of its status bits (``what`` names
+        the run in the refusal) -> ``(result, q)``."""
+        phi, q = self._params(alpha, scaling)
+        out = call(phi, q)
+        check_status(out["status"].reshape(-1), "MetranBatch(%s)" % what)
+        return out, q
+
     def get_mle(self, alpha=None):
         """``Metran.get_mle`` (metran.py:605-622) for every model: -2 log L ``[R]``."""
-        phi, q = self.kf.params_from_alpha(self._alpha(alpha), dt=self.dt)
-        return self.kf.loglik(phi, q)
+        return self.kf.loglik(*self._params(alpha))
 
     def solve(self, **kwargs):
         """``Metran.solve`` (metran.py:991-1045) for all models in lock-step (``calibrate_batch``);
@@ -149,45 +217,22 @@ class MetranBatch:
         self._cache.clear()
 
     # ------------------------------------------------------------------ cached kernel runs (Metran._run_kalman)
-    def _run(self, kind, alpha):
-        """kind: "project" (filter + projecting smoother: sim_means/sim_vars in ORIGINAL units), "smoother" (filter +
-        smoother with the state moments), "filter" (filter with the filtered moments), "loo" (leave-one-out predictions
-        loo_means/loo_vars in ORIGINAL units), "innov" (one-step-ahead innovations v/f in standardised units and forecasts
-        pred_mean/pred_var in ORIGINAL units), "dist" (the backward pair r/ninfo of the state disturbances, with the q they were
-        computed for).  One cached result per kind,
-        valid for the parameter set it was computed with (metran.py:978-989 keeps one too)."""
+    def _run(self, kind, alpha, request=None):
+        """The result of ``_KINDS[kind]`` for the parameter set and the (hashable) ``request``: from the cache, or from the engine
+        and then kept -- the keys of the kind's keep-list, nothing else.  A kind holds the results of one parameter set
+        (metran.py:978-989 keeps one too); another parameter set replaces them once its own run has passed the status check."""
         import torch
 
-        from .kalmanfilter import check_status
-
+        call, scaling, keep = _KINDS[kind]
         a = self._alpha(alpha)
         hit = self._cache.get(kind)
-        if hit is not None and hit[0].shape == a.shape and bool(torch.equal(hit[0], a)):
-            return hit[1]
-        phi, q = self.kf.params_from_alpha(a, dt=self.dt)
-        if kind == "project":
-            self.kf.set_scaling(self._std, self._mean)
-            out = self.kf.simulate_smoothed(phi, q)
-        elif kind == "smoother":
-            # state means + variances only (MK_OUT_VAR_ONLY): what the accessors below consume; the smoothed covariances
-            # [R,T,n,n] are never written (wide models: the state tape, BatchedKalman.state_tape_path)
-            out = self.kf.smooth_state_variances(phi, q)
-        elif kind == "filter":
-            out = self.kf.filter(phi, q, outputs=("F", "Pf"))
-        elif kind == "loo":
-            self.kf.set_scaling(self._std, self._mean)
-            out = self.kf.loo_predict(phi, q)
-        elif kind == "innov":
-            self.kf.set_scaling(self._std, self._mean)
-            out = self.kf.innovations(phi, q)
-        elif kind == "dist":
-            out = dict(self.kf.disturbances(phi, q))
-            out["q"] = q
-        else:
-            raise ValueError(kind)
-        check_status(out["status"], "MetranBatch(%s)" % kind)
-        self._cache[kind] = (a.clone(), out)
-        return out
+        if hit is None or hit[0].shape != a.shape or not bool(torch.equal(hit[0], a)):
+            hit = (a.clone(), {})
+        if request not in hit[1]:
+            out, q = self._launch(kind, a, scaling, lambda phi, q: call(self, phi, q, request))
+            hit[1][request] = {key: value for key, value in dict(out, q=q).items() if key in keep}
+            self._cache[kind] = hit
+        return hit[1][request]
 
     def _method(self, method):
         if method not in ("smoother", "filter"):
@@ -203,15 +248,57 @@ class MetranBatch:
         Z[:, :, self.N:] = self.kf.loadings
         return Z if standardized else Z * self._std[:, :, None]
 
+    # ------------------------------------------------------------------ what the accessors share
+    def _series(self, r, name):
+        names = list(self.batch.names[r])
+        if name not in names:
+            raise KeyError("Unknown name: " + str(name))  # the reference logs this and returns None (metran.py:881)
+        return names.index(name)
+
+    def _check_state(self, i):
+        if i < 0 or i >= self.N + self.K:
+            raise IndexError("Value of i must be >=0 and <%d" % (self.N + self.K))  # the reference logs and returns None
+
+    def _units(self, means, variances, standardized):
+        """``means`` and ``variances`` (or None) ``[..., R, steps, N]`` in ORIGINAL units, as they are or in standardised units."""
+        if not standardized:
+            return means, variances
+        std, mean = self._std[:, None, :], self._mean[:, None, :]
+        return (means - mean) / std, None if variances is None else variances / (std * std)
+
+    @staticmethod
+    def _band(mean, variance, ci):
+        from pandas import concat
+        from scipy.stats import norm
+
+        if ci is None:
+            return mean
+        if not (0 < ci < 1):
+            raise Exception("The value of alpha must be between 0 and 1.")  # metran.py:741-744, 868-871
+        iv = norm.ppf(1 - ci / 2.0) * np.sqrt(variance)
+        out = concat([mean, mean - iv, mean + iv], axis=1)
+        out.columns = ["mean", "lower", "upper"]
+        return out
+
+    def _series_band(self, r, j, means, variances, ci):
+        """Series ``j`` of model ``r`` of ``means`` / ``variances [R,T,N]``, cut to the model's length, on its index: ``_band``."""
+        L = int(self.batch.lengths[r])
+        sim = self.batch.frame(r, means[r].cpu().numpy()).iloc[:L, j]
+        return self._band(sim, self.batch.frame(r, variances[r].cpu().numpy()).iloc[:L, j] if ci is not None else None, ci)
+
+    def _rows(self, labels, names):
+        """Row labels ``(model, ...)``: ``labels(r)`` yields the rest of the rows of model ``r``, named ``names``; a model is
+        numbered by its place among ALL models (the shard's offset)."""
+        from pandas import MultiIndex
+
+        return MultiIndex.from_tuples([(r + self.shard[0],) + tuple(rest) for r in range(self.R) for rest in labels(r)],
+                                      names=["model"] + list(names))
+
     # ------------------------------------------------------------------ simulation (projection of the states)
     def _simulate(self, alpha, standardized, method):
         if self._method(method) == "smoother":
             out = self._run("project", alpha)  # fused epilogue, original units
-            means, variances = out["sim_means"], out["sim_vars"]
-            if standardized:
-                means = (means - self._mean[:, None, :]) / self._std[:, None, :]
-                variances = variances / (self._std * self._std)[:, None, :]
-            return means, variances
+            return self._units(out["sim_means"], out["sim_vars"], standardized)
         out = self._run("filter", alpha)
         key = ("simf", bool(standardized))
         if key not in out:
@@ -230,11 +317,7 @@ class MetranBatch:
     # ------------------------------------------------------------------ leave-one-out predictions (outlier screening)
     def _loo(self, alpha, standardized):
         out = self._run("loo", alpha)  # original units
-        means, variances = out["loo_means"], out["loo_vars"]
-        if standardized:
-            means = (means - self._mean[:, None, :]) / self._std[:, None, :]
-            variances = variances / (self._std * self._std)[:, None, :]
-        return means, variances
+        return self._units(out["loo_means"], out["loo_vars"], standardized)
 
     def get_loo_simulated_means(self, alpha=None, standardized=False):
         """Leave-one-out means ``[R,T,N]``: at every observed cell the series' value predicted from every OTHER observation
@@ -252,10 +335,7 @@ class MetranBatch:
         model ``r``: row t is what ``get_simulation`` returns at t after masking the observation at t alone; NaN rows where
         the series is not observed."""
         j = self._series(r, name)
-        means, variances = self._loo(alpha, standardized)
-        L = int(self.batch.lengths[r])
-        sim = self.batch.frame(r, means[r].cpu().numpy()).iloc[:L, j]
-        return self._band(sim, self.batch.frame(r, variances[r].cpu().numpy()).iloc[:L, j] if ci is not None else None, ci)
+        return self._series_band(r, j, *self._loo(alpha, standardized), ci)
 
     def get_deletion_residuals(self, alpha=None):
         """Deletion residuals ``[R,T,N]``: (y - loo mean) / sqrt(loo variance) at every observed cell, NaN elsewhere -- the
@@ -287,13 +367,7 @@ class MetranBatch:
         independent of the order of the series.  ``ci=None`` returns the mean Series."""
         j = self._series(r, name)
         out = self._run("innov", alpha)  # original units
-        means, variances = out["pred_mean"], out["pred_var"]
-        if standardized:
-            means = (means - self._mean[:, None, :]) / self._std[:, None, :]
-            variances = variances / (self._std * self._std)[:, None, :]
-        L = int(self.batch.lengths[r])
-        sim = self.batch.frame(r, means[r].cpu().numpy()).iloc[:L, j]
-        return self._band(sim, self.batch.frame(r, variances[r].cpu().numpy()).iloc[:L, j] if ci is not None else None, ci)
+        return self._series_band(r, j, *self._units(out["pred_mean"], out["pred_var"], standardized), ci)
 
     def test_whiteness(self, alpha=None, nlags=10, t_first=1):
         """Portmanteau (Ljung-Box) check of every series' standardised innovations: DataFrame indexed (model, series) with
@@ -304,17 +378,16 @@ class MetranBatch:
         subtracted for the estimated parameters (the textbook correction for a fitted ARMA model would use ``nlags - p``): the
         p-value is on the generous side for a calibrated model.  ``t_first=1`` leaves out the first step, whose prediction is
         the initial state's.  NaN where a series has no more than ``nlags`` cells or does not vary."""
-        from pandas import DataFrame, MultiIndex
+        from pandas import DataFrame
         from scipy.stats import chi2
 
         nlags = int(nlags)
         out = self._run("innov", alpha)
         stats = self.kf.innovation_stats(out["v"], out["f"], nlags=nlags, t_first=t_first).cpu().numpy()
-        index = MultiIndex.from_tuples([(r + self.shard[0], name) for r in range(self.R) for name in self.batch.names[r]],
-                                       names=["model", "series"])
         flat = stats.reshape(self.R * self.N, 4 + nlags)
         frame = DataFrame({"nobs": flat[:, 0].astype(np.int64), "mean": flat[:, 1], "var": flat[:, 2], "Q": flat[:, 3],
-                           "pvalue": chi2.sf(flat[:, 3], nlags)}, index=index)
+                           "pvalue": chi2.sf(flat[:, 3], nlags)},
+                          index=self._rows(lambda r: ((name,) for name in self.batch.names[r]), ["series"]))
         for l in range(1, nlags + 1):
             frame["r%d" % l] = flat[:, 3 + l]
         return frame
@@ -322,34 +395,12 @@ class MetranBatch:
     # ------------------------------------------------------------------ multi-step-ahead forecasts and their skill
     def _forecast(self, alpha, outputs, horizon=1, track_horizon=1, t_first=1, coverage=0.95):
         """``BatchedKalman.forecast`` for the parameter set: the cached kind "forecast", one result per REQUEST (outputs,
-        horizon, track horizon, first origin, coverage) of the parameter set it was computed with; fan and track in ORIGINAL
-        units, the fan from every model's last real step (``lengths[r] - 1``: shorter records are padded with empty steps)."""
-        import torch
-
-        from .kalmanfilter import check_status
-
-        a = self._alpha(alpha)
-        request = (tuple(outputs), int(horizon), int(track_horizon), int(t_first), float(coverage))
-        hit = self._cache.get("forecast")
-        if hit is None or hit[0].shape != a.shape or not bool(torch.equal(hit[0], a)):
-            hit = self._cache["forecast"] = (a.clone(), {})
-        if request not in hit[1]:
-            phi, q = self.kf.params_from_alpha(a, dt=self.dt)
-            self.kf.set_scaling(self._std, self._mean)
-            out = self.kf.forecast(phi, q, horizon=request[1], outputs=request[0], origins=np.asarray(self.batch.lengths, dtype=np.int64) - 1,
-                                   track_horizon=request[2], t_first=request[3], coverage=request[4])
-            check_status(out["status"], "MetranBatch(forecast)")
-            # the forward pass's workspace (the records: hundreds of times the outputs) is not kept: one entry per request
-            hit[1][request] = {k: v for k, v in out.items() if k != "_work"}
-        return hit[1][request]
+        horizon, track horizon, first origin, coverage); fan and track in ORIGINAL units."""
+        return self._run("forecast", alpha, (tuple(outputs), int(horizon), int(track_horizon), int(t_first), float(coverage)))
 
     def _forecast_moments(self, steps, alpha, standardized):
         out = self._forecast(alpha, ("fan",), horizon=steps)
-        means, variances = out["fan_mean"], out["fan_var"]
-        if standardized:
-            means = (means - self._mean[:, None, :]) / self._std[:, None, :]
-            variances = variances / (self._std * self._std)[:, None, :]
-        return means, variances
+        return self._units(out["fan_mean"], out["fan_var"], standardized)
 
     def get_forecast_means(self, steps=14, alpha=None, standardized=False):
         """OUT-OF-SAMPLE forecast means ``[R,steps,N]``: row h - 1 is the forecast of every series h steps after the model's
@@ -380,13 +431,7 @@ class MetranBatch:
         far ahead the model is worth anything.  ``horizon=1`` is ``get_prediction``."""
         j = self._series(r, name)
         out = self._forecast(alpha, ("track",), track_horizon=horizon)  # original units
-        means, variances = out["track_mean"], out["track_var"]
-        if standardized:
-            means = (means - self._mean[:, None, :]) / self._std[:, None, :]
-            variances = variances / (self._std * self._std)[:, None, :]
-        L = int(self.batch.lengths[r])
-        sim = self.batch.frame(r, means[r].cpu().numpy()).iloc[:L, j]
-        return self._band(sim, self.batch.frame(r, variances[r].cpu().numpy()).iloc[:L, j] if ci is not None else None, ci)
+        return self._series_band(r, j, *self._units(out["track_mean"], out["track_var"], standardized), ci)
 
     def forecast_skill(self, horizon=14, alpha=None, t_first=1, coverage=0.95):
         """Forecast skill by horizon, the out-of-sample counterpart of ``test_whiteness``: DataFrame indexed (model, series,
@@ -398,7 +443,7 @@ class MetranBatch:
         observations: the gain over predicting the series' mean.  NaN where ``nobs`` = 0.  Padding steps of a shorter record
         are empty and add no pairs."""
         import torch
-        from pandas import DataFrame, MultiIndex
+        from pandas import DataFrame
 
         horizon = int(horizon)
         out = self._forecast(alpha, ("skill",), horizon=horizon, t_first=t_first, coverage=coverage)
@@ -410,8 +455,7 @@ class MetranBatch:
         var = (torch.where(seen, obs - mean[:, None, :], torch.zeros_like(obs)) ** 2).sum(1) / cnt   # [R,N], divisor m
         var = np.repeat(var.cpu().numpy().reshape(-1), horizon)
         std = np.repeat(self._std.cpu().numpy().reshape(-1), horizon)
-        index = MultiIndex.from_tuples([(r + self.shard[0], name, h) for r in range(self.R) for name in self.batch.names[r]
-                                        for h in range(1, horizon + 1)], names=["model", "series", "horizon"])
+        index = self._rows(lambda r: ((name, h) for name in self.batch.names[r] for h in range(1, horizon + 1)), ["series", "horizon"])
         flat = s.reshape(-1, 6)
         with np.errstate(invalid="ignore", divide="ignore"):
             m = np.where(flat[:, 0] > 0, flat[:, 0], np.nan)
@@ -446,26 +490,10 @@ class MetranBatch:
         return steps
 
     def _weights(self, r, column, steps, what, alpha):
-        """``BatchedKalman.observation_weights`` for the targets (step, column) of model ``r``, run on a sub-engine that holds
-        that model alone (``BatchedKalman.subset``: the walks cost one pass over a record per target, the other models' records
-        are not touched): ``(w [M,T,N], intercept [M])`` on the device, in the filter's units; the cached kind "weights", one
-        result per request of the parameter set it was computed with."""
-        import torch
-
-        from .kalmanfilter import check_status
-
-        a = self._alpha(alpha)
-        request = (int(r), int(column), tuple(steps), what)
-        hit = self._cache.get("weights")
-        if hit is None or hit[0].shape != a.shape or not bool(torch.equal(hit[0], a)):
-            hit = self._cache["weights"] = (a.clone(), {})
-        if request not in hit[1]:
-            phi, q = self.kf.params_from_alpha(a, dt=self.dt)
-            targets = np.stack([np.asarray(steps, dtype=np.int64), np.full(len(steps), column, dtype=np.int64)], axis=1)
-            out = self.kf.subset([r]).observation_weights(phi[r:r + 1], q[r:r + 1], targets, what=what)
-            check_status(out["status"], "MetranBatch(weights)")
-            hit[1][request] = (out["weights"][0], out["intercept"][0])   # the workspace (records and gain tape) is not kept
-        return hit[1][request]
+        """``BatchedKalman.observation_weights`` for the targets (step, column) of model ``r``: ``(w [M,T,N], intercept [M])`` on
+        the device, in the filter's units; the cached kind "weights", one result per request (model, column, steps, what)."""
+        out = self._run("weights", alpha, (int(r), int(column), tuple(steps), what))
+        return out["weights"][0], out["intercept"][0]
 
     def _weight_frames(self, r, steps, w, intercept):
         from pandas import DataFrame
@@ -500,8 +528,7 @@ class MetranBatch:
     def get_state_weights(self, r, i, times, alpha=None):
         """``get_observation_weights`` for state ``i`` of model ``r`` (``get_state``'s mean), in the filter's units:
         ``sum w y_standardised + intercept`` is the smoothed state."""
-        if i < 0 or i >= self.N + self.K:
-            raise IndexError("Value of i must be >=0 and <%d" % (self.N + self.K))
+        self._check_state(i)
         steps = self._target_steps(r, times)
         w, intercept = self._weights(r, int(i), steps, "states", alpha)
         return self._weight_frames(r, steps, w, intercept)
@@ -578,8 +605,7 @@ class MetranBatch:
         on the model's index, as ``get_state`` returns the state itself; ``ci=None`` returns the mean Series."""
         from pandas import DataFrame
 
-        if i < 0 or i >= self.N + self.K:
-            raise IndexError("Value of i must be >=0 and <%d" % (self.N + self.K))
+        self._check_state(i)
         mean, variance = self.get_state_disturbances(alpha)
         L = int(self.batch.lengths[r])
         frame = lambda a: DataFrame(a[r, :L].cpu().numpy(), index=self.batch.index[r], columns=self._state_columns(r)).iloc[:, i]  # noqa: E731
@@ -593,16 +619,15 @@ class MetranBatch:
         treats the m residuals as independent; neighbouring ones are positively correlated, so the p-value is on the
         conservative side.  ``t_first=1`` leaves out the disturbance between the initial state and the first prediction.
         Rows with m = 0 carry NaN (``time`` NaT)."""
-        from pandas import DataFrame, MultiIndex, NaT
+        from pandas import DataFrame, NaT
         from scipy.stats import norm
 
         u = self.get_auxiliary_residuals(alpha, min_information).cpu().numpy()
-        rows, index = [], []
+        rows = []
         for r in range(self.R):
             L = int(self.batch.lengths[r])
             au = np.abs(u[r, int(t_first):L])
-            for i, name in enumerate(self._state_columns(r)):
-                index.append((r + self.shard[0], name))
+            for i in range(self.N + self.K):
                 m = int(np.isfinite(au[:, i]).sum())
                 if m == 0:
                     rows.append((np.nan, NaT, 0, np.nan))
@@ -611,17 +636,15 @@ class MetranBatch:
                 umax = float(au[t, i])
                 rows.append((umax, self.batch.index[r][t + int(t_first)], m, -np.expm1(m * np.log1p(-2.0 * norm.cdf(-umax)))))
         return DataFrame(rows, columns=["max_abs_u", "time", "nobs", "pvalue"],
-                         index=MultiIndex.from_tuples(index, names=["model", "state"]))
+                         index=self._rows(lambda r: ((name,) for name in self._state_columns(r)), ["state"]))
 
     # ------------------------------------------------------------------ posterior draws (simulation smoother)
+    # The draws and their window statistics go to the engine like the cached kinds (``_launch``) but are not kept: an ensemble is
+    # the size of the thing it summarises.
     def _draws(self, what, ndraws, seed, alpha, antithetic):
-        from .kalmanfilter import check_status
-
-        phi, q = self.kf.params_from_alpha(self._alpha(alpha), dt=self.dt)
-        self.kf.set_scaling(self._std, self._mean)
         # a model's instance number is its place among ALL models, so its draws do not depend on the number of ranks
-        out = self.kf.draw_smoothed(phi, q, ndraws, seed=seed, what=what, antithetic=antithetic, first_instance=self.shard[0])
-        check_status(out["status"].reshape(-1), "MetranBatch(draws of %s)" % what)
+        out, _ = self._launch("draws of %s" % what, alpha, True, lambda phi, q: self.kf.draw_smoothed(
+            phi, q, ndraws, seed=seed, what=what, antithetic=antithetic, first_instance=self.shard[0]))
         return out["draws"]
 
     def get_simulation_draws(self, ndraws, seed=0, alpha=None, standardized=False, antithetic=False):
@@ -630,10 +653,7 @@ class MetranBatch:
         mean, of a yearly minimum or of the time spent below a threshold is read off the ensemble (simulation smoother,
         Durbin & Koopman 2002; ``BatchedKalman.draw_smoothed``).  Where a series is observed a draw equals the observation.
         Draw ``s`` of a model is fixed by ``seed``: asking for more draws extends the ensemble, it does not change it."""
-        draws = self._draws("series", ndraws, seed, alpha, antithetic)  # original units
-        if standardized:
-            draws = (draws - self._mean[None, :, None, :]) / self._std[None, :, None, :]
-        return draws
+        return self._units(self._draws("series", ndraws, seed, alpha, antithetic), None, standardized)[0]  # the draws: original units
 
     def get_state_draws(self, ndraws, seed=0, alpha=None, antithetic=False):
         """``ndraws`` joint realisations of the states given the data, tensor ``[S,R,T,N+K]`` (``get_state_means`` is their
@@ -678,23 +698,20 @@ class MetranBatch:
         ``mean``, ``sd``, ``min``, ``max`` and one ``q<p>`` per probability; a window without a step of the model has count 0."""
         from pandas import DataFrame, MultiIndex
 
-        from .kalmanfilter import check_status
         from .windows import step_windows
 
         steps, starts = step_windows(self.batch.index, windows, self.T)
         probs = np.asarray(probs, dtype=np.float64).reshape(-1)
-        phi, q = self.kf.params_from_alpha(self._alpha(alpha), dt=self.dt)
-        self.kf.set_scaling(self._std, self._mean)
         # a model's instance number is its place among ALL models, so its statistics do not depend on the number of ranks
-        out = self.kf.draw_window_statistics(phi, q, ndraws, steps, thresholds=self._thresholds(thresholds), probs=probs, seed=seed,
-                                             antithetic=antithetic, first_instance=self.shard[0])
-        check_status(out["status"].reshape(-1), "MetranBatch(window statistics)")
+        out, _ = self._launch("window statistics", alpha, True, lambda phi, q: self.kf.draw_window_statistics(
+            phi, q, ndraws, steps, thresholds=self._thresholds(thresholds), probs=probs, seed=seed, antithetic=antithetic,
+            first_instance=self.shard[0]))
         summary = out["summary"].cpu().numpy()   # [R,N,W,5,5+P]
         functionals = ("mean", "min", "max", "fraction_below", "longest_spell")
         statistics = ["count", "mean", "sd", "min", "max"] + ["q%g" % p for p in probs]
-        rows = [(r + self.shard[0], name, start) for r in range(self.R) for name in self.batch.names[r] for start in starts[r]]
         values = [summary[r, :, : len(starts[r])].reshape(-1, len(functionals) * len(statistics)) for r in range(self.R)]
-        return DataFrame(np.concatenate(values, axis=0), index=MultiIndex.from_tuples(rows, names=["model", "series", "window"]),
+        return DataFrame(np.concatenate(values, axis=0),
+                         index=self._rows(lambda r: ((name, start) for name in self.batch.names[r] for start in starts[r]), ["series", "window"]),
                          columns=MultiIndex.from_product([functionals, statistics], names=["functional", "statistic"]))
 
     def get_window_statistic(self, r, name, windows, thresholds=None, ndraws=200, probs=(0.025, 0.5, 0.975), seed=0, alpha=None,
@@ -704,34 +721,12 @@ class MetranBatch:
         frame = self.get_window_statistics(windows, thresholds, ndraws, probs, seed, alpha, antithetic)
         return frame.loc[(r + self.shard[0], name)]
 
-    def _series(self, r, name):
-        names = list(self.batch.names[r])
-        if name not in names:
-            raise KeyError("Unknown name: " + str(name))  # the reference logs this and returns None (metran.py:881)
-        return names.index(name)
-
-    @staticmethod
-    def _band(mean, variance, ci):
-        from pandas import concat
-        from scipy.stats import norm
-
-        if ci is None:
-            return mean
-        if not (0 < ci < 1):
-            raise Exception("The value of alpha must be between 0 and 1.")  # metran.py:741-744, 868-871
-        iv = norm.ppf(1 - ci / 2.0) * np.sqrt(variance)
-        out = concat([mean, mean - iv, mean + iv], axis=1)
-        out.columns = ["mean", "lower", "upper"]
-        return out
-
+    # ------------------------------------------------------------------ one series' simulation and its decomposition
     def get_simulation(self, r, name, alpha=None, ci=0.05, standardized=False, method="smoother"):
         """``Metran.get_simulation`` (metran.py:831-883) for series ``name`` of model ``r``: DataFrame with
         ``mean`` (and ``lower``/``upper`` of the 1-ci interval; ``ci=None`` returns the mean Series)."""
         j = self._series(r, name)
-        means, variances = self._simulate(alpha, standardized, method)
-        L = int(self.batch.lengths[r])
-        sim = self.batch.frame(r, means[r].cpu().numpy()).iloc[:L, j]
-        return self._band(sim, self.batch.frame(r, variances[r].cpu().numpy()).iloc[:L, j] if ci is not None else None, ci)
+        return self._series_band(r, j, *self._simulate(alpha, standardized, method), ci)
 
     def decompose_simulation(self, r, name, alpha=None, standardized=False, method="smoother"):
         """``Metran.decompose_simulation`` (metran.py:885-942): DataFrame with the specific dynamic component
@@ -777,7 +772,6 @@ class MetranBatch:
 
     def get_state(self, r, i, alpha=None, ci=0.05, method="smoother"):
         """``Metran.get_state`` (metran.py:713-756): state ``i`` of model ``r`` with its 1-ci band."""
-        if i < 0 or i >= self.N + self.K:
-            raise IndexError("Value of i must be >=0 and <%d" % (self.N + self.K))  # the reference logs and returns None
+        self._check_state(i)
         mean = self.get_state_means(r, alpha, method).iloc[:, i]
         return self._band(mean, self.get_state_variances(r, alpha, method).iloc[:, i] if ci is not None else None, ci)

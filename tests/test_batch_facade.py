@@ -91,3 +91,112 @@ def test_facade_on_examples_data(g1):
     np.testing.assert_allclose(fit.alpha[0].cpu().numpy(), gs["optimal"], rtol=1e-2)
     sim2 = mb.get_simulation(0, "B21B0214005")                # default parameters = the optimum just found
     np.testing.assert_allclose(sim2.values[:50], g1["get_simulation_005"], rtol=0, atol=2e-3)
+
+
+# ---- the result cache on the real engine: launches, bits and what is held ----
+def _narrow():
+    """2 models x (3,1), T = 40: an ahead-of-time shape of at most 16 states -- ``project`` and ``smoother`` read filtered records."""
+    from batch_standin import two_models
+
+    models, G = two_models()
+    return models, G, np.array([[8.0, 6.0, 9.0, 12.0], [5.0, 7.0, 8.0, 10.0]]), {}
+
+
+def _wide():
+    """2 models x (32,4), T = 20, loadings given (no factor analysis): ``project`` and ``smoother`` read the filter's tape."""
+    from metran_amd.synthetic import make_dfm_batch
+
+    d = make_dfm_batch(2, 32, 4, 20, seed=7, missing=0.2)
+    idx = pd.date_range("2002-03-01", periods=20, freq="D")
+    models = []
+    for r in range(2):
+        obs = d["obs"][r].copy()
+        obs[:6] = np.where(np.isfinite(obs[:6]), obs[:6], 0.1)      # every series has its cross-sectional pairs
+        models.append([pd.Series(obs[:, j] * (1.0 + j) + j, index=idx, name="s%d" % j).dropna() for j in range(32)])
+    return models, d["loadings"], np.full((2, 36), 9.0), {"min_pairs": 5}
+
+
+def _same_bits(a, b):
+    import torch
+
+    if isinstance(a, torch.Tensor):
+        return a.shape == b.shape and bool(torch.equal(a, b) or torch.equal(torch.nan_to_num(a, nan=1e300), torch.nan_to_num(b, nan=1e300)))
+    if isinstance(a, (tuple, list)):
+        return len(a) == len(b) and all(_same_bits(x, y) for x, y in zip(a, b))
+    if isinstance(a, dict):
+        return list(a) == list(b) and all(_same_bits(a[k], b[k]) and a[k].attrs == b[k].attrs for k in a)
+    return type(a) is type(b) and a.equals(b) and a.index.equals(b.index)
+
+
+@pytest.mark.parametrize("shape", [_narrow, _wide], ids=["3x1-T40", "32x4-T20"])
+def test_cache_launches_once_and_holds_outputs_only(shape):
+    """One accessor of every cached kind twice (and the accessors that derive something from a held result): the engine's launch
+    counters move on the first call and not on the second; the second result has the bits of the first and of a fresh facade's;
+    and no held tensor -- nor the storage behind it -- is larger than the largest array the kind's accessors read, which the
+    forward pass's workspace, the filtered records and the tape all are (32 to 2560 doubles per model and step at these shapes)."""
+    import torch
+
+    from metran_amd.batch import MetranBatch
+
+    models, G, alpha, kwargs = shape()
+    mb, fresh = MetranBatch(models, factors=G, **kwargs), MetranBatch(models, factors=G, **kwargs)
+    R, T, N, K = mb.R, mb.T, mb.N, mb.K
+    n, name, H, steps = N + K, "s1", 5, [3, 11]
+    assert (R, N, K) == (2,) + G.shape[1:] and T == {3: 40, 32: 20}[N]
+    # kind -> (its accessors, the first of which runs the engine; the elements of the largest array those accessors read)
+    kinds = {
+        "project": ([lambda m: m.get_simulated_means(alpha), lambda m: m.get_simulated_variances(alpha, standardized=True),
+                     lambda m: m.get_simulation(1, name, alpha)], R * T * N),
+        # the decomposition holds one component per factor and series: cdf [R,K,T,N]
+        "smoother": ([lambda m: m.get_state_means(1, alpha), lambda m: m.get_state_variances(0, alpha), lambda m: m.get_state(0, n - 1, alpha),
+                      lambda m: m.decompose_simulation(1, name, alpha), lambda m: m.decompose_simulation(1, name, alpha, standardized=True)],
+                     R * T * max(n, K * N)),
+        # the projection of the filtered states reads the whole filtered covariance Pf [R,T,n,n]
+        "filter": ([lambda m: m.get_state_variances(1, alpha, method="filter"), lambda m: m.get_simulated_variances(alpha, method="filter"),
+                    lambda m: m.decompose_simulation(0, name, alpha, method="filter")], R * T * max(n * n, K * N)),
+        "loo": ([lambda m: m.get_loo_simulated_means(alpha), lambda m: m.get_deletion_residuals(alpha)], R * T * N),
+        "innov": ([lambda m: m.get_innovations(alpha), lambda m: m.get_prediction(1, name, alpha), lambda m: m.test_whiteness(alpha, nlags=3)],
+                  R * T * N),
+        "dist": ([lambda m: m.get_state_disturbances(alpha), lambda m: m.get_auxiliary_residuals(alpha)], R * T * n),
+        # fan [R,H,N], track [R,T,N], skill [R,N,H,6]
+        "forecast": ([lambda m: m.get_forecast_means(H, alpha), lambda m: m.get_forecast(1, name, H, alpha)], R * N * max(T, 6 * H)),
+        # one model's weights [M,T,N]
+        "weights": ([lambda m: m.get_observation_weights(1, name, steps, alpha), lambda m: m.get_weight_shares(1, name, steps, alpha)],
+                    len(steps) * T * N),
+    }
+    # the weights run on a sub-engine of their model, whose launches the facade's engine does not count: its creation is counted
+    subsets = []
+    subset = mb.kf.subset
+    mb.kf.subset = lambda index: subsets.append(index) or subset(index)
+    mb.kf.enable_timing(accumulate=True)
+
+    def launches():
+        """Filter and smoother launches (the record readers are booked as smoothers) and sub-engines since the previous call."""
+        _, nf, _, ns = mb.kf.kernel_ms_totals()
+        count = nf + ns + len(subsets)
+        subsets.clear()
+        return count
+
+    for kind, (accessors, _) in kinds.items():
+        for i, accessor in enumerate(accessors):
+            launches()
+            one = accessor(mb)
+            assert (launches() > 0) == (i == 0), (kind, i)    # the kind's first accessor runs the engine, the others read its result
+            assert kind in mb._cache
+            two = accessor(mb)
+            assert launches() == 0, (kind, i)
+            assert _same_bits(one, two) and _same_bits(two, accessor(fresh)), (kind, i)
+    mb.get_prediction_at(0, name, 3, alpha), mb.forecast_skill(H, alpha)          # the other outputs of a forecast
+    assert set(mb._cache) == set(kinds)
+
+    def tensors(x):
+        if isinstance(x, torch.Tensor):
+            yield x
+        for v in (x.values() if isinstance(x, dict) else x if isinstance(x, (tuple, list)) else ()):
+            yield from tensors(v)
+
+    for kind, (_, bound) in kinds.items():
+        held = list(tensors(mb._cache[kind][1]))
+        assert held, kind
+        for t in held:
+            assert t.numel() <= bound and t.untyped_storage().nbytes() <= 8 * bound, (kind, tuple(t.shape), bound)

@@ -148,8 +148,7 @@ def _stand_in(models, loadings):
     """A MetranBatch whose engine answers ``disturbances`` from dist_adjoint (the constructor itself needs a GPU)."""
     import torch
 
-    from metran_amd.batch import MetranBatch
-    from metran_amd.ingest import ObservationBatch
+    from batch_standin import stand_in
     from oracle_engine import OracleEngine
 
     class DisturbanceEngine(OracleEngine):
@@ -167,42 +166,17 @@ def _stand_in(models, loadings):
             return {"r": torch.from_numpy(np.stack(rr)), "ninfo": torch.from_numpy(np.stack(nn)),
                     "status": torch.full((phi.shape[0],), self.status_bits, dtype=torch.int32)}
 
-    batch = ObservationBatch(models)
-    mean = np.nanmean(batch.obs, axis=1)
-    std = np.nanstd(batch.obs, axis=1, ddof=1)
-    mb = MetranBatch.__new__(MetranBatch)
-    mb.batch = batch
-    mb.kf = DisturbanceEngine((batch.obs - mean[:, None]) / std[:, None], loadings)
-    mb.R, mb.T, mb.N = batch.shape
-    mb.K = loadings.shape[2]
-    mb.dt, mb.shard, mb.alpha, mb._cache = 1.0, (0, mb.R), None, {}
-    mb._std, mb._mean = torch.from_numpy(std), torch.from_numpy(mean)
-    return mb
-
-
-def _two_models():
-    import pandas as pd
-
-    rng = np.random.default_rng(4)
-    idx = pd.date_range("2001-01-01", periods=40, freq="D")
-    models = []
-    for r in range(2):
-        cols = []
-        for j in range(3):
-            s = pd.Series(10.0 * (j + 1) + (2.0 + j) * np.cumsum(rng.normal(size=40)) / 3.0, index=idx, name="s%d" % j)
-            cols.append(s[rng.random(40) > 0.3])
-        models.append(cols if r == 0 else [c.iloc[: len(c) - 4] for c in cols])
-    G = np.broadcast_to(np.array([[0.6], [0.5], [-0.4]]), (2, 3, 1)).copy()
-    return models, G
+    return stand_in(DisturbanceEngine, models, loadings)
 
 
 def test_metran_batch_accessors_over_a_stand_in_engine():
     from scipy.stats import norm
 
+    from batch_standin import two_models
     from metran_amd._lib import MetranHipError
     from metran_amd.params import phi_q_from_alpha
 
-    models, G = _two_models()
+    models, G = two_models()
     mb = _stand_in(models, G)
     alpha = np.array([[8.0, 6.0, 9.0, 12.0], [5.0, 7.0, 8.0, 10.0]])
     phi, q = phi_q_from_alpha(alpha, G, 1.0)

@@ -191,8 +191,7 @@ def _stand_in(models, loadings):
     """A MetranBatch whose engine answers from the oracle and the restatement (the constructor itself needs a GPU)."""
     import torch
 
-    from metran_amd.batch import MetranBatch
-    from metran_amd.ingest import ObservationBatch
+    from batch_standin import stand_in
     from oracle_engine import OracleEngine
 
     class DrawEngine(OracleEngine):
@@ -215,34 +214,14 @@ def _stand_in(models, loadings):
             status = torch.full((ndraws, phi.shape[0]), self.status_bits, dtype=torch.int32)
             return {"draws": torch.from_numpy(np.stack(out, axis=1)), "status": status}
 
-    batch = ObservationBatch(models)
-    mean = np.nanmean(batch.obs, axis=1)
-    std = np.nanstd(batch.obs, axis=1, ddof=1)
-    mb = MetranBatch.__new__(MetranBatch)
-    mb.batch = batch
-    mb.kf = DrawEngine((batch.obs - mean[:, None]) / std[:, None], loadings)
-    mb.R, mb.T, mb.N = batch.shape
-    mb.K = loadings.shape[2]
-    mb.dt, mb.shard, mb.alpha, mb._cache = 1.0, (0, mb.R), None, {}
-    mb._std, mb._mean = torch.from_numpy(std), torch.from_numpy(mean)
-    return mb
+    return stand_in(DrawEngine, models, loadings)
 
 
 def test_metran_batch_accessors_over_a_stand_in_engine():
-    import pandas as pd
-
+    from batch_standin import two_models
     from metran_amd._lib import MetranHipError
 
-    rng = np.random.default_rng(4)
-    idx = pd.date_range("2001-01-01", periods=40, freq="D")
-    models = []
-    for r in range(2):
-        cols = []
-        for j in range(3):
-            s = pd.Series(10.0 * (j + 1) + (2.0 + j) * np.cumsum(rng.normal(size=40)) / 3.0, index=idx, name="s%d" % j)
-            cols.append(s[rng.random(40) > 0.3])
-        models.append(cols if r == 0 else [c.iloc[: len(c) - 4] for c in cols])
-    G = np.broadcast_to(np.array([[0.6], [0.5], [-0.4]]), (2, 3, 1)).copy()
+    models, G = two_models()
     mb = _stand_in(models, G)
     alpha = np.full((2, 4), 8.0)
     S = 3

@@ -129,43 +129,6 @@ def test_unused_and_out_of_range_targets_are_nan():
 
 
 # ---- MetranBatch over a stand-in engine ----
-def _stand_in(models, loadings):
-    """A MetranBatch whose engine answers ``observation_weights`` from weights_ref and ``simulate_smoothed`` from the oracle
-    (the constructor itself needs a GPU)."""
-    import torch
-
-    from metran_amd.batch import MetranBatch
-    from metran_amd.ingest import ObservationBatch
-
-    batch = ObservationBatch(models)
-    mean = np.nanmean(batch.obs, axis=1)
-    std = np.nanstd(batch.obs, axis=1, ddof=1)
-    mb = MetranBatch.__new__(MetranBatch)
-    mb.batch = batch
-    mb.kf = WeightsEngine((batch.obs - mean[:, None]) / std[:, None], loadings)
-    mb.R, mb.T, mb.N = batch.shape
-    mb.K = loadings.shape[2]
-    mb.dt, mb.shard, mb.alpha, mb._cache = 1.0, (0, mb.R), None, {}
-    mb._std, mb._mean = torch.from_numpy(std), torch.from_numpy(mean)
-    return mb
-
-
-def _two_models():
-    import pandas as pd
-
-    rng = np.random.default_rng(4)
-    idx = pd.date_range("2001-01-01", periods=40, freq="D")
-    models = []
-    for r in range(2):
-        cols = []
-        for j in range(3):
-            s = pd.Series(10.0 * (j + 1) + (2.0 + j) * np.cumsum(rng.normal(size=40)) / 3.0, index=idx, name="s%d" % j)
-            cols.append(s[rng.random(40) > 0.3])
-        models.append(cols if r == 0 else [c.iloc[: len(c) - 4] for c in cols])
-    G = np.broadcast_to(np.array([[0.6], [0.5], [-0.4]]), (2, 3, 1)).copy()
-    return models, G
-
-
 def _shortest_window(aw, tstar, mass):
     """Brute force: the shortest [a, b] with a <= tstar <= b holding ``mass`` of sum(aw), the earliest among equals."""
     tot, best = aw.sum(), None
@@ -178,12 +141,15 @@ def _shortest_window(aw, tstar, mass):
 
 
 def test_metran_batch_accessors_over_a_stand_in_engine():
+    """The engine answers ``observation_weights`` from weights_ref and ``simulate_smoothed`` from the oracle
+    (tests/weights_engine.py)."""
     import pandas as pd
 
+    from batch_standin import stand_in, two_models
     from metran_amd.params import phi_q_from_alpha
 
-    models, G = _two_models()
-    mb = _stand_in(models, G)
+    models, G = two_models()
+    mb = stand_in(WeightsEngine, models, G)
     alpha = np.array([[8.0, 6.0, 9.0, 12.0], [5.0, 7.0, 8.0, 10.0]])
     phi, q = phi_q_from_alpha(alpha, G, 1.0)
     L = [int(v) for v in mb.batch.lengths]
