@@ -13,20 +13,22 @@ the Durbin-Koopman backward pair (r_t, N_t) of every step, from which
 import numpy as np
 
 
-def dist_adjoint(obs, phi, q, loadings, obsvar=None, x0=None, P0=None, variant=None):
+def dist_adjoint(obs, phi, q, loadings, obsvar=None, x0=None, P0=None, variant=None, dtype=np.float64):
     """One model, obs [T,N] (NaN = missing).  -> (r [T,n], ninfo [T,n]) = (r_t, diag N_t), as the kernels store them (a
     negative diagonal from rounding is 0).  ``variant``: a deliberately WRONG read-out, for the tests that show the right one
     can be told from it -- "after_phi" (read after the pull-back through Phi), "before_updates" (read before the step's
-    updates are pulled back), "no_rr" (Pb's diagonal without the r^2 term), "shifted" (outputs one step late)."""
+    updates are pulled back), "no_rr" (Pb's diagonal without the r^2 term), "shifted" (outputs one step late).  ``dtype``: the
+    arithmetic of both passes -- ``np.float64`` (the default) or ``np.longdouble``, the yardstick of the property sweep."""
     obs = np.asarray(obs, float)
     Tn, N = obs.shape
     K = loadings.shape[1]
     n = N + K
-    R = np.zeros(N) if obsvar is None else np.asarray(obsvar, float)
-    xi = np.zeros(n) if x0 is None else np.array(x0, float)
-    Pi = np.eye(n) if P0 is None else np.array(P0, float)
-    Z = np.concatenate([np.eye(N), loadings], axis=1)
-    F, Pf = np.zeros((Tn, n)), np.zeros((Tn, n, n))
+    phi, q = np.asarray(phi, dtype=dtype), np.asarray(q, dtype=dtype)
+    R = np.zeros(N, dtype=dtype) if obsvar is None else np.asarray(obsvar, dtype=dtype)
+    xi = np.zeros(n, dtype=dtype) if x0 is None else np.array(x0, dtype=dtype)
+    Pi = np.eye(n, dtype=dtype) if P0 is None else np.array(P0, dtype=dtype)
+    Z = np.concatenate([np.eye(N), loadings], axis=1).astype(dtype)
+    F, Pf = np.zeros((Tn, n), dtype=dtype), np.zeros((Tn, n, n), dtype=dtype)
     x, P = xi.copy(), Pi.copy()
     for t in range(Tn):
         x = phi * x
@@ -39,14 +41,14 @@ def dist_adjoint(obs, phi, q, loadings, obsvar=None, x0=None, P0=None, variant=N
             x = x + d * v / f
             P = P - np.outer(d, d) / f
         F[t], Pf[t] = x, P
-    rr, nn = np.zeros((Tn, n)), np.zeros((Tn, n))
+    rr, nn = np.zeros((Tn, n), dtype=dtype), np.zeros((Tn, n), dtype=dtype)
 
     def read(t, xb, Pb):
         r = -0.5 * xb
         rr[t] = r
         nn[t] = np.diag(Pb) + (0.0 if variant == "no_rr" else r * r)
 
-    xb, Pb = np.zeros(n), np.zeros((n, n))
+    xb, Pb = np.zeros(n, dtype=dtype), np.zeros((n, n), dtype=dtype)
     for t in range(Tn - 1, -1, -1):
         x = phi * (F[t - 1] if t > 0 else xi)
         P = np.outer(phi, phi) * (Pf[t - 1] if t > 0 else Pi) + np.diag(q)

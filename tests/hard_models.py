@@ -1,7 +1,8 @@
 """Seeded generator of "hard" dynamic-factor models for the property sweeps (test infrastructure; used by the GPU tier's
 tests/test_gpu_property.py and, on the CPU, by tests/test_property_generator.py, which runs the SAME sweep through the oracle
 and the numpy restatements so that every tolerance below is known to hold between two independent implementations before
-a GPU minute is spent on it).
+a GPU minute is spent on it; the diagnostic routes -- disturbances, forecasts, observation weights, draws -- take the same
+sweep in tests/test_gpu_property_diagnostics.py / tests/test_property_diagnostics.py, with the bars at the end of this file).
 
 A group = B models of one shape (N, K) and one length T (a launch needs a common T), each model drawn independently:
   persistence   phi = exp(-1/alpha), alpha ~ U(2, 60) (Metran's parametrisation, metran.py:246-263); in 30 % of the models one
@@ -200,3 +201,73 @@ def smoother_tolerance(g, b, ref):
     correct implementations of the reference's formulas differ by that much (tests/test_dk_tape.py, property test)."""
     big = max(1.0, float(np.abs(ref["Pp"]).max()), float(np.abs(ref["F"]).max()))
     return 1e-9 * big + 4e-15 * big * big / float(g["q"][b].min())
+
+
+# ------------------------------------------------------------------------------------------ the diagnostic routes' bars
+# Each bar has the form of filter_tolerances: (the tier's own flat bar + MARGIN * measured * conditioning) * max(1, largest
+# modulus of the quantity).  ``measured`` is not chosen: it is the largest (float64 restatement - longdouble restatement) /
+# (conditioning * scale) that scripts/measure_diagnostic_bars.py finds over the default sweep and 30 further ones
+# (METRAN_SWEEP_SEED = 1 .. 30; 10 912 models); its output is quoted in the docstrings.  MARGIN = 4: the kernels sum in tree order
+# with fused multiply-adds -- another sample of the same rounding process -- and the filter's bars leave about 2 x (0.52 measured,
+# 1.0 allowed); 4 keeps room for unseen seeds and still rejects the 1e-6-sized error of a dropped term.  ``margin=1`` is what
+# tests/test_property_diagnostics.py holds the two restatements to.
+MARGIN = 4.0
+RAW_TOL = 1e-12         # tests/test_disturbance_gpu.py::RAW_TOL
+FORECAST_ATOL_MEAN = 1e-12   # tests/test_forecast_gpu.py::ATOL_MEAN
+FORECAST_RTOL_VAR = 1e-12    # tests/test_forecast_gpu.py::RTOL_VAR
+WEIGHTS_BAR = 1e-13     # tests/test_weights_gpu.py::BAR
+DRAW_TOL = 1e-9         # tests/test_draws_gpu.py::TOL, the smoothed-moment bar: smoother_tolerance's flat part
+PERTURB_TOL = 1e-11     # tests/test_draws_gpu.py::PERTURB_TOL
+# the last line of scripts/measure_diagnostic_bars.py (31 sweeps, 10 912 models):
+MEASURED = {"dist_r": 0.43, "dist_n": 2.1, "forecast_mean": 0.18, "forecast_var": 0.62, "weights_series": 0.47, "weights_states": 0.86}
+
+
+def _top(a):
+    a = np.abs(np.asarray(a, dtype=np.float64))
+    return max(1.0, float(np.nanmax(a))) if np.isfinite(a).any() else 1.0
+
+
+def disturbance_tolerances(g, b, ref, r, ninfo, margin=MARGIN):
+    """(atol of r, atol of ninfo) of model b against disturbance_ref.dist_adjoint in longdouble; ``r``, ``ninfo``: that
+    reference (their largest moduli are the scales).  Measured, float64 against longdouble restatement in units of
+    conditioning * scale: r 0.228 (default sweep) / 0.425, 0.365, 0.266 (seeds 1-10, 11-20, 21-30), the largest at seed 2,
+    (7,2) T = 7, "none"; ninfo 1.32 / 2.11, 1.88, 1.50, the largest at seed 4, (6,2) T = 4, "last".  The largest gaps themselves
+    are 2.05e-08 (r: seed 6, (5,1) T = 7, "iid", min q 4.3e-9, ratio 0.14) and 1.47e-07 (ninfo: seed 18, (5,1) T = 46, "none", min q
+    3.4e-9, ratio 0.56).  ninfo's ratio is about five times r's -- N_t accumulates squares of what r_t accumulates once -- but it
+    is the same on ordinary models (min q ~ 0.03: up to 2.1) and on the 2 510 models whose conditioning exceeds 1e-10 (up to 1.3),
+    over six orders of magnitude of min q: it scales with the conditioning, and no other scale (the largest 1 / f) is needed."""
+    c = conditioning(g, b, ref)
+    return (RAW_TOL + margin * MEASURED["dist_r"] * c) * _top(r), (RAW_TOL + margin * MEASURED["dist_n"] * c) * _top(ninfo)
+
+
+def forecast_tolerances(g, b, ref, means, margin=MARGIN):
+    """(atol of a forecast mean, rtol of a forecast variance) of model b against forecast_ref in longdouble; ``means``: the
+    reference's means in play (the scale of the mean is max(1, max |y|, max |mean|), as tests/test_forecast_gpu.py's).
+    Measured over the whole table (every origin, 14 horizons), in units of conditioning (* scale for the mean): mean 0.0456
+    (default sweep) / 0.178, 0.110, 0.178 (seeds 1-10, 11-20, 21-30), the largest at seed 1, (8,2) T = 38, "series"; variance
+    0.259 / 0.432, 0.530, 0.622, the largest at seed 30, (2,1) T = 23, "last".  Largest gaps: 5.0e-09 (mean: seed 8, (3,1)
+    T = 49, "first", min q 2.3e-9) and 3.6e-08 relative (variance: seed 14, (5,1) T = 33, "steps", min q 2.4e-9)."""
+    c = conditioning(g, b, ref)
+    return ((FORECAST_ATOL_MEAN + margin * MEASURED["forecast_mean"] * c) * max(_top(g["obs"][b]), _top(means)),
+            FORECAST_RTOL_VAR + margin * MEASURED["forecast_var"] * c)
+
+
+def weights_tolerance(g, b, ref, w, what="series", margin=MARGIN):
+    """atol of the weights and the intercept of ONE target of model b against weights_ref.weights in longdouble; ``w``: the
+    reference's weights of that target.  Measured over the sweep's targets (tests/diagnostic_sweep.py::targets), relative to
+    max(1, max |w|) and in units of conditioning: series 0.384 (default sweep) / 0.472, 0.435, 0.389 (seeds 1-10, 11-20, 21-30),
+    states 0.209 / 0.864, 0.306, 0.407, both largest at seed 5, (2,1) T = 39, "last", min q 7.7e-6.  Largest gaps: 1.2e-08
+    (series: seed 8, (3,1) T = 49, "first") and 3.0e-08 (states: seed 6, (5,1) T = 7, "iid")."""
+    c = conditioning(g, b, ref)
+    return (WEIGHTS_BAR + margin * MEASURED["weights_" + what] * c) * _top(w)
+
+
+def draw_tolerance(g, b, ref_star, xplus, what="series"):
+    """atol of one posterior draw of model b against draw_ref.draw_model.  A draw is x+ + E[x | y*]: the unconditional path
+    (the perturb tier's PERTURB_TOL on the scale of x+) plus a smoothing pass of the record y* = y - y+, NOT of y -- so the
+    smoother's bar is ``smoother_tolerance`` on the oracle's moments of THAT record (``ref_star``: hard_models.oracle_model of
+    the group with y* in place of y).  Nothing is measured here: both parts are bars of existing tiers.  A series draw is a
+    projection z_j' x: both parts times the largest absolute row sum of Z = [I | loadings] (at most 1 + sqrt(K): a row of the
+    loadings has at most unit length)."""
+    rows = float((1.0 + np.abs(g["loadings"][b]).sum(1)).max()) if what == "series" else 1.0
+    return rows * (smoother_tolerance(g, b, ref_star) + PERTURB_TOL * _top(xplus))

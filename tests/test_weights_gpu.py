@@ -186,6 +186,50 @@ def test_against_restatement(case, T):
     _check_case(N, K, T, family, time_major, full, seed=100 * N + T)
 
 
+PER_RECORD_SHAPES = [(8, 2), (15, 2)]   # the 16-lane groups and the one-wavefront walk
+PER_RECORD_T = 17
+
+
+def _per_record_case(N, K):
+    """B = 5 on R = 2 with target lists that differ between the two records in every slot: (problem, {what: targets [2,M,2]})."""
+    T = PER_RECORD_T
+    p = _data(N, K, T, seed=23 + N, full=True)
+    n = N + K
+    tg = {"series": np.array([[(7, 0), (5, 2), (0, 0), (T - 1, 1)], [(9, 3), (2, 1), (T - 1, 0), (3, 2)]], dtype=np.int64),
+          "states": np.array([[(8, N), (8, 1)], [(3, n - 1), (12, 0)]], dtype=np.int64)}
+    return p, tg
+
+
+def _other_records_list(p, b, tg, what):
+    """What instance b would get from the OTHER record's target list (on its own record and parameters): a kernel that reads
+    one list for every record returns this for the instances of one of the two."""
+    return _reference(p, b, tg[::-1], what)[0]
+
+
+@pytest.mark.parametrize("shape", PER_RECORD_SHAPES, ids=["%dx%d" % s for s in PER_RECORD_SHAPES])
+def test_every_record_has_its_own_target_list(shape):
+    """weights_walk_kernel reads targets[(rec * M + m) * 2]: the other tests hand it ONE list broadcast to the records.  Here the
+    two records' lists differ, every instance is compared at BAR with the restatement on ITS record's list, and is more than
+    1000 BAR from what the other record's list gives (tests/test_weights_host.py shows that of the restatement itself)."""
+    N, K = shape
+    p, tgs = _per_record_case(N, K)
+    kf = _engine(p)
+    for what, tg in tgs.items():
+        got = _raw(kf, p, tg, what, time_major=(what == "states"))
+        assert not got["status"].any()
+        for b in range(B_):
+            (w, ic), _ = _reference(p, b, tg, what)
+            wo, io = _other_records_list(p, b, tg, what)
+            seen = np.isfinite(p["obs"][b % R_])
+            for m in range(tg.shape[1]):
+                g, what_m = got["weights"][b, m], "%s target %s of instance %d" % (what, tuple(tg[b % R_, m]), b)
+                assert np.array_equal(np.isnan(g), ~seen), what_m
+                wm = w[m].astype(np.float64)
+                bar = BAR * max(1.0, np.nanmax(np.abs(wm)))
+                assert np.nanmax(np.abs(g - wm)) <= bar and abs(got["intercept"][b, m] - float(ic[m])) <= bar, what_m
+                assert np.nanmax(np.abs(g - wo[m].astype(np.float64))) > 1000 * bar, what_m
+
+
 @pytest.fixture
 def no_jit(monkeypatch, tmp_path):
     """A machine without hipcc and without prebuilt modules: a shape outside the ahead-of-time list runs the size-generic filter."""

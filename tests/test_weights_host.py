@@ -121,6 +121,23 @@ def test_wrong_variants_are_far_outside_the_bar(bad):
     assert np.nanmax(np.abs(wrong[0] - g["weights"])) > 1e6 * PARITY_BAR
 
 
+def test_the_gpu_tiers_per_record_target_lists_tell_the_records_apart():
+    """tests/test_weights_gpu.py::test_every_record_has_its_own_target_list relies on this: on its inputs the restatement with
+    an instance's own list is more than 2000 bars from the restatement with the other record's list, target by target -- so a
+    kernel within one bar of the first is more than 1000 bars from the second."""
+    import test_weights_gpu as tw
+
+    for N, K in tw.PER_RECORD_SHAPES:
+        p, tgs = tw._per_record_case(N, K)
+        for what, tg in tgs.items():
+            assert tg.shape[0] == tw.R_ and all(tuple(a) != tuple(b) for a, b in zip(tg[0], tg[1]))
+            for b in range(tw.B_):
+                (w, ic), gain = tw._reference(p, b, tg, what, dtype=F64)
+                (wo, io), _ = tw._reference(p, b, tg[::-1], what, gain, dtype=F64)
+                for m in range(tg.shape[1]):
+                    assert np.nanmax(np.abs(w[m] - wo[m])) > 2000 * tw.BAR * max(1.0, np.nanmax(np.abs(w[m]))), (N, K, what, b, m)
+
+
 def test_unused_and_out_of_range_targets_are_nan():
     y, phi, q, G, R, x0, P0 = _model(3, 1, 12, 5, True)
     for what, cols in (("series", 3), ("states", 4)):
