@@ -1194,6 +1194,19 @@ __global__ void __launch_bounds__(256) smoother_record_kernel(SmootherArgs a)
         }
         double delta = xs - phi_r * xfc; // xs[t+1] - Xp[t+1]; formed early so that it is "old" when DPP-read
         if constexpr (G == 16) dpp_pin(delta);
+        // FACTOR_FWD (16-lane groups, n <= 10): stage 0 of the factorisation as ldlt_factor has it, then stages 1..n-1 with the
+        // forward substitution and the D^-1 scaling of the solve folded into the pivot chains (Sweeps<n>::factor_forward,
+        // DESIGN.md section 4) -- z leaves it as D^-1 L^-1 W.  Full-square records only: measured at c2 the packed-symmetric
+        // form gains nothing from it (1.556 -> 1.576 and 1.586 -> 1.590 ms on two machines, full-square 1.732 -> 1.648) and
+        // stays on the separate factorisation and forward sweep
+        constexpr bool FACTOR_FWD = (G == 16) && Sweeps<n>::fused_factor && !SYM;
+        if constexpr (FACTOR_FWD) {
+            // D is formed HERE, at the top of the step: left to itself the compiler sinks the subtractions towards their use,
+            // keeps A's and Ps[t+1]'s rows alive next to the registers factorised in place and pays n register moves a step
+            // (measured with the pins behind stage 0, where the subtractions would cover its chain: 0.05 ms slower at c2)
+#pragma unroll
+            for (int c = 0; c < n; ++c) dpp_pin(D[c]);
+        }
 
         if constexpr (DEFER)
             if (recS) RIO::gather_all(imgS, rmap, etmp); // the record of step t+1, put there at the end of its iteration
@@ -1201,12 +1214,32 @@ __global__ void __launch_bounds__(256) smoother_record_kernel(SmootherArgs a)
         // ---- A = L D L^T, right-looking; lane c ends up holding L(c, j) in A[j] for j < c ----
         if constexpr (G == 16) dpp_guard(A); // A is compiler-produced (build-time hazard check)
         double dinv[n];
-        ldlt_factor<n, G, false>(A, dinv, pivmin);
+        if constexpr (FACTOR_FWD) {
+            ldlt_stage0<G>(A[0], dinv[0], pivmin);
+            Sweeps<n>::factor_forward(A, z, dinv, pivmin);
+        } else {
+            ldlt_factor<n, G, false>(A, dinv, pivmin);
+        }
         if (__builtin_expect(__ballot(!(pivmin > 0.0)) != 0ull, 0)) { // a null direction (cold): pinv-like redo
 #pragma unroll
-            for (int c = 0; c < n; ++c) A[c] = fma(phi_r, z[c], qd[c]);
+            for (int c = 0; c < n; ++c) {
+                if constexpr (FACTOR_FWD) {
+                    // The fused sweep has overwritten W and Pfc still holds Pf[t]: W = Pf Phi again.  Through an opaque copy,
+                    // or the compiler shares these products (and with them A) with the ones at the top of the step, keeps both
+                    // alive across the factorisation and pays 2n register moves in every hot step for this cold block.
+                    double pf = Pfc[c];
+                    dpp_pin(pf);
+                    z[c] = pf * phic[c];
+                }
+                A[c] = fma(phi_r, z[c], qd[c]);
+            }
             if constexpr (G == 16) dpp_guard(A);
             ldlt_factor<n, G, true>(A, dinv, pivmin);
+            if constexpr (FACTOR_FWD) {
+                Sweeps<n>::forward(z, A);
+#pragma unroll
+                for (int c = 0; c < n; ++c) z[c] *= dinv[c];
+            }
         }
         // Consume the chunks of step t-1 (requested one iteration ago) and request those of step t-2 BEFORE this
         // iteration's stores are issued.  Loads and stores share vmcnt and complete out of order with respect to each
@@ -1229,7 +1262,8 @@ __global__ void __launch_bounds__(256) smoother_record_kernel(SmootherArgs a)
         // statement per broadcast-FMA, hipcc pads every sweep boundary with an s_nop (31 issue slots per step at n = 10)
         constexpr bool FUSED = (G == 16) && Sweeps<n>::fused;
         // ---- lane i solves A z = W_i  (row i of J = Pf Phi^T A^{-1}, :458-460) ----
-        if constexpr (FUSED) {
+        if constexpr (FACTOR_FWD) { // forward substitution and D^{-1}: done with the factorisation
+        } else if constexpr (FUSED) {
             Sweeps<n>::forward(z, A);
         } else {
             sfor<0, n>(MK_LAMBDA(kc) { // forward: L y = b;  z[c] -= L(c,k) y_k, L(c,k) lives in lane c
@@ -1237,8 +1271,10 @@ __global__ void __launch_bounds__(256) smoother_record_kernel(SmootherArgs a)
                 Gp::template axpy_col<k + 1, n, true, n>(z, A[k], z[k]);
             });
         }
+        if constexpr (!FACTOR_FWD) {
 #pragma unroll
-        for (int c = 0; c < n; ++c) z[c] *= dinv[c]; // D^{-1}
+            for (int c = 0; c < n; ++c) z[c] *= dinv[c]; // D^{-1}
+        }
         if constexpr (FUSED) {
             Sweeps<n>::backward(z, A);
         } else {

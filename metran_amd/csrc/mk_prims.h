@@ -562,6 +562,15 @@ __device__ __forceinline__ void ldlt_factor(double (&A)[n], double (&dinv)[n], d
         A[j] = lr;
     });
 }
+// Stage 0 of ldlt_factor<n, G, false> on its own: Sweeps<n>::factor_forward (mk_sweeps.h) takes over from stage 1.
+template <int G>
+__device__ __forceinline__ void ldlt_stage0(double &a0, double &dinv0, double &pivmin)
+{
+    const double piv = Group<G>::template bcast<0>(a0); // d_0
+    pivmin = min_f64(pivmin, piv);
+    dinv0 = rcp_nr(piv);
+    a0 *= dinv0; // L(r, 0)
+}
 // status bits of a smoother instance from the smallest pivot it met (covariances of standardised series are
 // O(1): -1e-8 is far outside rounding)
 __device__ __forceinline__ unsigned pivot_flags(double pivmin)

@@ -273,7 +273,9 @@ TEST_SHAPES = [(7, 2), (11, 3), (14, 2), (20, 2), (16, 2), (32, 1), (48, 3), (17
                # tests/shape_matrix.py: both sides of every compile-time switch of the kernels
                (12, 4), (13, 4), (20, 6), (23, 5), (33, 4), (40, 4), (59, 4), (60, 4),
                # tests/test_filter_emit_gpu.py: the smallest state (one update a step: every slot of the deferred emission collapses)
-               (1, 1)]
+               (1, 1),
+               # tests/test_factor_forward_gpu.py: n = 7 and n = 10 with three factors (the fused factor-and-forward sweep)
+               (4, 3), (7, 3)]
 
 
 if __name__ == "__main__":

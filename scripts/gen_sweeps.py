@@ -19,6 +19,153 @@ def stmt(lines, outs, ins, indent="        "):
     return "%sasm volatile(\n%s\n%s    : %s\n%s    : %s);\n" % (indent, body, indent, ", ".join(outs), indent, ", ".join(ins) if ins else "")
 
 
+class Ins:
+    """One instruction of the fused factor-and-forward stream over SYMBOLIC registers (A[c], z[c], dinv[c], pivmin, piv, e):
+    `fmt` takes the registers `regs` in order; `dpp` is the register read through DPP (src0), `trans` a transcendental."""
+
+    def __init__(self, fmt, regs, writes, reads, dpp=None, trans=False):
+        self.fmt, self.regs, self.writes, self.reads, self.dpp, self.trans = fmt, regs, writes, reads, dpp, trans
+
+
+def _fmac(acc, src, mul, lane):
+    return Ins("v_fmac_f64_dpp {0}, {1}, -{2} row_newbcast:%d%s" % (lane, DPP), [acc, src, mul], acc, {acc, src, mul}, dpp=src)
+
+
+def _scale(c):
+    return Ins("v_mul_f64 {0}, {0}, {1}", ["z[%d]" % c, "dinv[%d]" % c], "z[%d]" % c, {"z[%d]" % c, "dinv[%d]" % c})
+
+
+FILL_WANT = 8  # independent instructions a stage wants: two ahead of the pivot broadcast, one in every later gap of the chain
+
+
+def fused_stream(n):
+    """Stages 1..n-1 of the right-looking LDL^T with the forward substitution of the right-hand sides folded in (the
+    elimination of [Pp | W]) and the D^-1 scaling behind it, as ONE instruction stream.  Entry: stage 0 is done (A[0] holds
+    L(., 0), dinv[0] = 1/d_0, both fresh: A[0] counts as written by the instruction before the stream).
+    Stage j: the column-j multiply-add of stage j-1's trailing update first, then the pivot broadcast (two wait states behind
+    it), v_rcp_f64, the three refinement multiply-adds and L(., j) = A[j] / d_j -- every one of them with an INDEPENDENT
+    instruction in front: the rest of stage j-1's trailing update, substitution stage j-1 (column j-1 of L is final), and in
+    the late stages, which have few of either, z[c] *= dinv[c] of the columns the substitution has passed.  Every value is
+    produced by the operation that produces it in ldlt_factor / Sweeps::forward / the caller's scaling loop."""
+    age = {}            # register -> wait states since its last VALU write (absent: old)
+    last_trans = [None]
+    out = []
+
+    def emit(i):
+        out.append(i)
+        for r in list(age):
+            age[r] += 1
+        age[i.writes] = 0
+        last_trans[0] = i.writes if i.trans else None
+
+    def nop(k):
+        out.append(Ins("s_nop %d" % (k - 1), [], None, set()))
+        for r in list(age):
+            age[r] += k
+        last_trans[0] = None
+
+    def ready(i):
+        return (i.dpp is None or age.get(i.dpp, 99) >= 2) and not (last_trans[0] in i.reads and not i.trans)
+
+    def must(i):
+        need = 0
+        if i.dpp is not None:
+            need = max(need, 2 - age.get(i.dpp, 99))
+        if last_trans[0] in i.reads and not i.trans:
+            need = max(need, 1)
+        if need > 0:
+            nop(need)
+        emit(i)
+
+    age["A[0]"] = 0
+    pool = []           # columns whose y_c the substitution has passed: z[c] may take its D^-1
+    for j in range(1, n):
+        lr, y, a, d = "A[%d]" % (j - 1), "z[%d]" % (j - 1), "A[%d]" % j, "dinv[%d]" % j
+        if j >= 2:
+            pool.append(j - 2)
+        fills = [_fmac("A[%d]" % c, "A[%d]" % c, lr, j - 1) for c in range(j + 1, n)]
+        fills += [_fmac("z[%d]" % c, lr, y, c) for c in range(j, n)]
+        chain = [Ins("v_mov_b64_dpp {0}, {1} row_newbcast:%d%s" % (j, DPP), ["piv", a], "piv", {a}, dpp=a),
+                 Ins("v_rcp_f64 {0}, {1}", [d, "piv"], d, {"piv"}, trans=True),
+                 Ins("v_fma_f64 {0}, -{1}, {2}, 1.0", ["e", "piv", d], "e", {"piv", d}),
+                 Ins("v_fma_f64 {0}, {0}, {0}, {0}", ["e"], "e", {"e"}),
+                 Ins("v_fma_f64 {0}, {0}, {1}, {0}", [d, "e"], d, {d, "e"})]
+        if j < n - 1:
+            chain.append(Ins("v_mul_f64 {0}, {0}, {1}", [a, d], a, {a, d}))
+        vmin = Ins("v_min_f64 {0}, {0}, {1}", ["pivmin", "piv"], "pivmin", {"pivmin", "piv"})
+        take = min(len(pool), max(0, FILL_WANT - len(fills)))
+        fills += [_scale(pool.pop(0)) for _ in range(take)]
+        # the gaps in front of the chain instructions, and the one behind the last (ahead of the next stage's first
+        # multiply-add); scarce fills go to the latency gaps of the refinement first, then ahead of the broadcast.
+        # v_min_f64 (off the chain) always follows v_rcp_f64: the wait state a transcendental result needs.
+        gaps = [2, 1, 1, 1, 1, 1][:len(chain)] + [1]
+        have, want = len(fills), [0] * len(gaps)
+        for g in [3, 4, 5, 2, 6, 1, 0, 0]:
+            if g < len(gaps) and have > 0 and want[g] < gaps[g]:
+                want[g] += 1
+                have -= 1
+        want[-1] += have    # what is left runs behind the stage's last chain instruction
+        must(_fmac(a, a, lr, j - 1))
+        for g in range(len(want)):
+            for _ in range(want[g]):
+                pick = next((f for f in fills if ready(f)), fills[0])
+                fills.remove(pick)
+                must(pick)
+            if g < len(chain):
+                must(chain[g])
+                if chain[g].trans:
+                    emit(vmin)
+        assert not fills
+    for c in pool + [n - 2, n - 1]:     # y_{n-2} and y_{n-1} are final only now
+        must(_scale(c))
+    return out
+
+
+def operands(ins_list):
+    """(register, constraint) of one statement: read before written -> "v" / "+v", written first -> "=&v"."""
+    order, first_read, written = [], set(), set()
+    for i in ins_list:
+        for r in i.regs:
+            if r not in order:
+                order.append(r)
+        for r in i.reads:
+            if r not in written:
+                first_read.add(r)
+        if i.writes:
+            written.add(i.writes)
+    ops = [(r, "+v" if r in first_read else "=&v") for r in order if r in written]
+    ops += [(r, "v") for r in order if r not in written]
+    return ops
+
+
+def op_count(ops):
+    return sum(2 if c == "+v" else 1 for _, c in ops)
+
+
+def gen_fused(n):
+    """Sweeps<n>::factor_forward: the stream cut into as few statements of <= 30 operands as its order allows."""
+    stream, stmts, cur = fused_stream(n), [], []
+    for i in stream:
+        if cur and op_count(operands(cur + [i])) > 30:
+            stmts.append(cur)
+            cur = []
+        cur.append(i)
+    stmts.append(cur)
+    s = "    static constexpr bool fused_factor = true;\n"
+    s += "    // stages 1..%d of A = L D L^T with L y = b folded into the pivot chain and z = D^-1 y behind it; stage 0 is the caller's\n" % (n - 1)
+    s += "    static __device__ __forceinline__ void factor_forward(double (&A)[%d], double (&z)[%d], double (&dinv)[%d], double &pivmin)\n    {\n" % (n, n, n)
+    s += "        double piv, e;\n"
+    for st in stmts:
+        ops = operands(st)
+        idx = {r: "%%%d" % k for k, (r, _) in enumerate(ops)}
+        lines = [i.fmt.format(*[idx[r] for r in i.regs]) for i in st]
+        outs = ['"%s"(%s)' % (c, r) for r, c in ops if c != "v"]
+        ins = ['"v"(%s)' % r for r, c in ops if c == "v"]
+        s += stmt(lines, outs, ins)
+    s += "    }\n"
+    return s
+
+
 def gen(n):
     s = "template <>\nstruct Sweeps<%d> {\n    static constexpr bool fused = true;\n" % n
     # forward substitution: z[c] -= bcast_c(A[k]) z[k], k = 0..n-2, c = k+1..n-1     (operands: z 0..n-1, A n..2n-2)
@@ -57,7 +204,7 @@ def gen(n):
         for k in ks:
             ins += ['"v"(z[%d])' % k, '"v"(V[%d])' % k]
         s += stmt(lines, ['"+v"(P[%d])' % c for c in range(n)], ins)
-    s += "    }\n};\n\n"
+    s += "    }\n" + gen_fused(n) + "};\n\n"
     return s
 
 
@@ -67,7 +214,7 @@ def blocks(n, size):
 
 def gen_tiled(n):
     """11 <= n <= 16: the same five sweeps, each as a short sequence of <= 30-operand statements."""
-    s = "template <>\nstruct Sweeps<%d> {\n    static constexpr bool fused = true;\n" % n
+    s = "template <>\nstruct Sweeps<%d> {\n    static constexpr bool fused = true;\n    static constexpr bool fused_factor = false; // tiled shapes: ldlt_factor, then forward\n" % n
     KB = blocks(n, 7)
 
     def tri(forward):
@@ -150,7 +297,8 @@ def render():
          "// The DPP source operands of every statement (A, D, delta, z of the LAST sweep) are old values: the callers keep\n"
          "// the two wait states between their producers and the statement (dpp_guard), scripts/check_dpp_hazards.py checks.\n"
          "#pragma once\n\n"
-         "template <int n>\nstruct Sweeps {\n    static constexpr bool fused = false; // wider groups: the per-FMA primitives of Group<16>\n};\n\n")
+         "template <int n>\nstruct Sweeps {\n    static constexpr bool fused = false; // wider groups: the per-FMA primitives of Group<16>\n"
+         "    static constexpr bool fused_factor = false;\n};\n\n")
     for n in range(2, 11):
         h += gen(n)
     h += ("// 11 <= n <= 16: a statement takes at most 30 operands -- every sweep is tiled into a few statements (blocks of 7\n"
