@@ -76,7 +76,8 @@ typedef struct mk_problem {
     int64_t n_records;   /* R, 1 <= R <= B */
     int64_t T, N, K;
     int64_t warmup;            /* get_mle(warmup), metran/kalmanfilter.py:550; Metran uses 1 */
-    const double *d_obs;       /* [R,T,N]  observations, NaN/inf = missing (kalmanfilter.py:657) */
+    const double *d_obs;       /* [R,T,N]  observations, NaN/inf = missing (kalmanfilter.py:657); read by the filters and, to tell
+                                  the fully observed steps, by mk_smooth / mk_filter_smooth (see mk_smooth) */
     const double *d_phi;       /* [B,n]    diag of transition_matrix      (metran.py:283-290) */
     const double *d_q;         /* [B,n]    diag of transition_covariance  (metran.py:310-322) */
     const double *d_loadings;  /* [R,N,K]  observation_matrix[:, N:]      (metran.py:365-370) */
@@ -179,7 +180,10 @@ MK_API int mk_sync(mk_context *ctx);
 /* Two shape classes have a second, equivalent kernel kept for A/B measurements (both tested against the oracle:
  * tests/test_smoother_variants.py, tests/test_hip_parity.py).  value 0 = the default.  There is no environment
  * variable and no switch that changes results.
- *   MK_VARIANT_SMOOTHER16     n <= 15, packed records: 0 smoother_record_kernel (DPP), 1 smoother_blk_kernel (4x4x4 MFMA)
+ *   MK_VARIANT_SMOOTHER16     n <= 15, packed records: 0 smoother_record_kernel (DPP), 1 smoother_blk_kernel (4x4x4 MFMA),
+ *                             2 smoother_record_kernel with the general covariance products at EVERY step: without it, for
+ *                             n <= 10, full-square records, no epilogue and d_obsvar == NULL, a step at which the model observed
+ *                             all N series (read from prob->d_obs) takes the rank-K form of the same products
  *   MK_VARIANT_WIDE_SMOOTHER  n > 16: 0 the blocked MFMA smoother (n <= 36: rows of A folded into the idle lanes),
  *                             1 smoother_wave_kernel (round 1, row per lane; built for n <= 51, MK_ERR_SHAPE above),
  *                             2 the MFMA smoother without the fold
@@ -599,7 +603,12 @@ MK_API int mk_observation_weights(mk_context *ctx, const mk_problem *prob, doubl
 /* kalmansmoother for B instances (kalmanfilter.py:403-476).  Reads out->d_F and out->d_Pf
  * (as written by mk_filter); predicted moments are recomputed from them (Phi diagonal), so
  * d_Xp/d_Pp are not read.  Writes d_S, d_Ps (either may be NULL), d_status.  d_status is OVERWRITTEN (cleared on the context's
- * stream, then the smoother's bits), as by mk_smooth_dense; only mk_filter_smooth keeps the filter's bits beside the smoother's. */
+ * stream, then the smoother's bits), as by mk_smooth_dense; only mk_filter_smooth keeps the filter's bits beside the smoother's.
+ * Also READS prob->d_obs (as does the smoother half of mk_filter_smooth) when prob->d_obsvar == NULL and prob->d_loadings is given,
+ * for n <= 10 and full-square records without projection outputs: which steps observe every series decides the form of the covariance
+ * products there (MK_VARIANT_SMOOTHER16).  The observations must be the ones out->d_F / d_Pf were filtered from, unchanged since
+ * mk_filter; pass d_obs = NULL (or MK_VARIANT_SMOOTHER16 = 2) to smooth moments that come from elsewhere.  A per-record summary of
+ * them is kept in the context: mk_observations_changed() after changing them in place. */
 MK_API int mk_smooth(mk_context *ctx, const mk_problem *prob, const mk_outputs *out);
 
 /* run_smoother (kalmanfilter.py:676-694): mk_filter then mk_smooth on the same stream. */

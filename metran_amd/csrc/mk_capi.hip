@@ -35,6 +35,14 @@ struct mk_context {
     // mk_observations_changed() since (the solver evaluates the objective ~80 times on one uploaded record)
     const double *tlist_obs;
     long tlist_T, tlist_N, tlist_ostep;
+    // which records take the record smoother's rank-K covariance step (mk::launch_full_records): device bytes [R] and "any of them",
+    // counted once per observation set -- same pointer, shape and layout, and no mk_observations_changed() since
+    unsigned char *lr_take;
+    long lr_cap;
+    int *lr_any_dev;
+    const double *lr_obs;
+    long lr_R, lr_T, lr_N, lr_bs;
+    int lr_any;
     int variant[MK_VARIANT_COUNT]; // mk_set_kernel_variant: which of two equivalent (tested) kernels serves a shape class
     double *gws;       // workspace of the size-generic smoother (mk_generic.hip), grown on demand
     size_t gws_cap;    // ... in doubles
@@ -172,8 +180,15 @@ hipError_t dispatch_smoother(mk_context *ctx, int N, int K, const mk::SmootherAr
     // need the exact (N, K)
     const bool proj = a.sim_means || a.sim_vars || a.tape != 0;
     const bool force_generic = ctx->variant[MK_VARIANT_KERNEL_FAMILY] == 1;
-    if (!force_generic)
-        if (const mk::ShapeOps *o = find_ops(N, K, !proj)) return o->smoother(a, s);
+    if (!force_generic) {
+        if (const mk::ShapeOps *o = find_ops(N, K)) return o->smoother(a, s);
+        if (!proj)
+            if (const mk::ShapeOps *o = find_ops(N, K, true)) {
+                mk::SmootherArgs b = a; // a kernel of the same n but another (N, K): the rank-K step reads the loadings as [N, K]
+                b.obs = nullptr;
+                return o->smoother(b, s);
+            }
+    }
     if (generic_shape(N, K)) {
         mk::GenericSmootherArgs g;
         g.a = a;
@@ -320,6 +335,12 @@ MK_API int mk_create(int device, mk_context **out)
     ctx->tlist_cap = 0;
     ctx->tlist_obs = nullptr;
     ctx->tlist_T = ctx->tlist_N = ctx->tlist_ostep = 0;
+    ctx->lr_take = nullptr;
+    ctx->lr_cap = 0;
+    ctx->lr_any_dev = nullptr;
+    ctx->lr_obs = nullptr;
+    ctx->lr_R = ctx->lr_T = ctx->lr_N = ctx->lr_bs = 0;
+    ctx->lr_any = 0;
     ctx->gws = nullptr;
     ctx->gws_cap = 0;
     ctx->lb_counters = nullptr;
@@ -489,6 +510,8 @@ MK_API int mk_destroy(mk_context *ctx)
         }
     if (ctx->tlist) (void)hipFree(ctx->tlist);
     if (ctx->gws) (void)hipFree(ctx->gws);
+    if (ctx->lr_take) (void)hipFree(ctx->lr_take);
+    if (ctx->lr_any_dev) (void)hipFree(ctx->lr_any_dev);
     if (ctx->lb_counters) (void)hipFree(ctx->lb_counters);
     (void)mk_comm_destroy(ctx);
     delete ctx;
@@ -498,7 +521,7 @@ MK_API int mk_destroy(mk_context *ctx)
 MK_API int mk_set_stream(mk_context *ctx, void *s)
 {
     MK_CTX(ctx);
-    if (ctx->stream != (hipStream_t)s) ctx->tlist_obs = nullptr; // the cached observed-step list was built in the OLD stream's order
+    if (ctx->stream != (hipStream_t)s) ctx->tlist_obs = ctx->lr_obs = nullptr; // the cached observed-step list and the records' flags were built in the OLD stream's order
     ctx->stream = (hipStream_t)s;
     return MK_OK;
 }
@@ -507,9 +530,8 @@ MK_API int mk_set_kernel_variant(mk_context *ctx, int which, int value)
 {
     MK_CTX(ctx);
     if (which < 0 || which >= MK_VARIANT_COUNT) return fail(MK_ERR_INVALID, "mk_set_kernel_variant: unknown selector %d", which);
-    if (value < 0 || value > ((which == MK_VARIANT_SMOOTHER16 || which == MK_VARIANT_SINGLE_RECORD || which == MK_VARIANT_KERNEL_FAMILY ||
-                               which == MK_VARIANT_TAPE_FILTER) ? 1 : 2))
-        return fail(MK_ERR_INVALID, "mk_set_kernel_variant: value must be 0 or 1 (0, 1 or 2 for the two wide selectors)");
+    if (value < 0 || value > ((which == MK_VARIANT_SINGLE_RECORD || which == MK_VARIANT_KERNEL_FAMILY || which == MK_VARIANT_TAPE_FILTER) ? 1 : 2))
+        return fail(MK_ERR_INVALID, "mk_set_kernel_variant: value must be 0 or 1 (0, 1 or 2 for the smoother selectors and the wide filter)");
     ctx->variant[which] = value;
     return MK_OK;
 }
@@ -526,6 +548,7 @@ MK_API int mk_observations_changed(mk_context *ctx)
 {
     MK_CTX(ctx);
     ctx->tlist_obs = nullptr;
+    ctx->lr_obs = nullptr;
     return MK_OK;
 }
 
@@ -807,6 +830,55 @@ static int do_filter(mk_context *ctx, const mk_problem *p, const mk_outputs *o)
     return MK_OK;
 }
 
+// The records for which the record smoother takes its rank-K covariance step: at least 7 of 8 of the record's steps observe every
+// series.  Counted on the device once per observation set (the count reads every cell; the answer is kept until the pointer, the
+// shape or the layout changes or mk_observations_changed() is called) and read back once, so that a launch in which no record
+// qualifies runs the parent's kernel.  *take = nullptr: do not take the step (also while the stream is being captured and the
+// answer is not there yet: the read-back would need a synchronisation).
+static hipError_t full_records(mk_context *ctx, const mk_problem *p, const unsigned char **take)
+{
+    *take = nullptr;
+    const long bs = p->obs_time_major ? 1 : p->T;
+    if (!(ctx->lr_obs == p->d_obs && ctx->lr_R == p->n_records && ctx->lr_T == p->T && ctx->lr_N == p->N && ctx->lr_bs == bs)) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(ctx->stream, &cap) != hipSuccess) (void)hipGetLastError();
+        if (cap != hipStreamCaptureStatusNone) return hipSuccess;
+        ctx->lr_obs = nullptr;
+        if (ctx->lr_cap < p->n_records) {
+            if (ctx->lr_take) {
+                hipError_t e = hipStreamSynchronize(ctx->stream); // a launch still reading the old buffer
+                if (e != hipSuccess) return e;
+                (void)hipFree(ctx->lr_take);
+                ctx->lr_take = nullptr;
+                ctx->lr_cap = 0;
+            }
+            hipError_t e = hipMalloc((void **)&ctx->lr_take, (size_t)p->n_records);
+            if (e != hipSuccess) return e;
+            ctx->lr_cap = p->n_records;
+        }
+        if (!ctx->lr_any_dev) {
+            hipError_t e = hipMalloc((void **)&ctx->lr_any_dev, sizeof(int));
+            if (e != hipSuccess) return e;
+        }
+        hipError_t e = hipMemsetAsync(ctx->lr_any_dev, 0, sizeof(int), ctx->stream);
+        if (e != hipSuccess) return e;
+        e = mk::launch_full_records(p->n_records, p->T, (int)p->N, bs, p->obs_time_major ? p->n_records : 1, p->d_obs, ctx->lr_take,
+                                    ctx->lr_any_dev, ctx->stream);
+        if (e != hipSuccess) return e;
+        e = hipMemcpyAsync(&ctx->lr_any, ctx->lr_any_dev, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
+        if (e != hipSuccess) return e;
+        e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) return e;
+        ctx->lr_obs = p->d_obs;
+        ctx->lr_R = p->n_records;
+        ctx->lr_T = p->T;
+        ctx->lr_N = p->N;
+        ctx->lr_bs = bs;
+    }
+    if (ctx->lr_any) *take = ctx->lr_take;
+    return hipSuccess;
+}
+
 // clear_status: the smoother kernels OR their bits into d_status -- behind mk_filter_smooth the filter's stay, called on its own mk_smooth
 // WRITES the word: it is cleared on the stream once every argument check has passed, right before the launch
 static int do_smooth(mk_context *ctx, const mk_problem *p, const mk_outputs *o, bool clear_status)
@@ -820,7 +892,7 @@ static int do_smooth(mk_context *ctx, const mk_problem *p, const mk_outputs *o, 
     mk::SmootherArgs a;
     a.tape = tape;
     a.obsvar = tape ? p->d_obsvar : nullptr;
-    a.variant = (ctx->variant[MK_VARIANT_SMOOTHER16] ? 1 : 0) | (ctx->variant[MK_VARIANT_WIDE_SMOOTHER] == 1 ? 2 : 0) |
+    a.variant = (ctx->variant[MK_VARIANT_SMOOTHER16] == 1 ? 1 : 0) | (ctx->variant[MK_VARIANT_WIDE_SMOOTHER] == 1 ? 2 : 0) |
                 (ctx->variant[MK_VARIANT_WIDE_SMOOTHER] == 2 ? 4 : 0);
     a.rs = 0;
     a.sym = 0;
@@ -851,6 +923,24 @@ static int do_smooth(mk_context *ctx, const mk_problem *p, const mk_outputs *o, 
     } else if (o->d_sim_means || o->d_sim_vars || sym || var) {
         return fail(MK_ERR_INVALID, "d_sim_means / d_sim_vars, MK_OUT_PACKED_SYM and MK_OUT_VAR_ONLY need the record layout "
                                     "(record_stride = mk_record_stride[_sym](n))");
+    }
+    // the record smoother's rank-K covariance step (smoother_record_kernel, LR) rests on R = 0: the guard is the NULL pointer, not
+    // the values behind it.  MK_VARIANT_SMOOTHER16 = 2 keeps the general products at every step
+    a.obs = nullptr;
+    a.lr_take = nullptr;
+    a.obs_bs = a.obs_ts = 0;
+    // (the kernel addresses a cell by a 32-bit byte offset from a base that walks in time: observations below 4 GiB)
+    if (p->d_obs && p->d_loadings && !p->d_obsvar && !tape && ctx->variant[MK_VARIANT_SMOOTHER16] != 2 &&
+        (double)p->n_records * (double)p->T * (double)p->N * sizeof(double) < 4294967296.0) {
+        // ... and only for shapes and record forms whose kernel has the step (everything else never looks at the observations)
+        const bool served = !sym && !var && o->record_stride && !(o->d_sim_means || o->d_sim_vars) && p->N + p->K <= 10 &&
+                            ctx->variant[MK_VARIANT_SMOOTHER16] == 0 && ctx->variant[MK_VARIANT_KERNEL_FAMILY] == 0;
+        if (served) MK_HIP(full_records(ctx, p, &a.lr_take));
+        if (a.lr_take) {
+            a.obs = p->d_obs;
+            a.obs_bs = p->obs_time_major ? 1 : p->T;
+            a.obs_ts = p->obs_time_major ? p->n_records : 1;
+        }
     }
     a.R = p->n_records;
     a.loadings = p->d_loadings;

@@ -139,4 +139,36 @@ hipError_t launch_pack(long RT, int N, const double *obs, double *observations, 
     return hipGetLastError();
 }
 
+// Which records the record smoother's rank-K covariance step is taken for (smoother_record_kernel LR): one
+// 256-thread block per record counts the steps at which every series is observed -- exactly, so the answer does not depend on T
+// or on where a sample would fall -- and sets take[r] where they are at least 7 of 8.  Record (r, t) at row r*obs_bs + t*obs_ts.
+__global__ void __launch_bounds__(256)
+full_records_kernel(long T, int N, long obs_bs, long obs_ts, const double *obs, unsigned char *take, int *any)
+{
+    __shared__ unsigned s_cnt;
+    if (threadIdx.x == 0) s_cnt = 0u;
+    __syncthreads();
+    const double *src = obs + (long)blockIdx.x * obs_bs * N;
+    unsigned cnt = 0;
+    for (long t = threadIdx.x; t < T; t += 256) {
+        bool full = true;
+        for (int j = 0; j < N; ++j) full = full && isfinite(src[t * obs_ts * N + j]);
+        cnt += full ? 1u : 0u;
+    }
+    atomicAdd(&s_cnt, cnt);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const bool ok = 8ull * s_cnt >= 7ull * (unsigned long long)T;
+        take[blockIdx.x] = ok ? 1 : 0;
+        if (ok) atomicOr(any, 1);
+    }
+}
+
+hipError_t launch_full_records(long R, long T, int N, long obs_bs, long obs_ts, const double *obs, unsigned char *take, int *any,
+                               hipStream_t s)
+{
+    hipLaunchKernelGGL(full_records_kernel, dim3((unsigned)R), dim3(256), 0, s, T, N, obs_bs, obs_ts, obs, take, any);
+    return hipGetLastError();
+}
+
 } // namespace mk

@@ -94,6 +94,12 @@ struct SmootherArgs {
     long tape;           // 1: F is the backward tape (MK_OUT_TAPE, rs = tape_stride(N, K)): smoother_dk_kernel (mk_dk.hip);
                          // 2: the STATE tape (rs = state_tape_stride(N, K)): state_means / state_vars [., n] are written too
     const double *obsvar; // tape path: observation variances [R,N] or NULL = zeros
+    // smoother_record_kernel's rank-K covariance step: the observations, record (r, t) at row r*obs_bs + t*obs_ts as in FilterArgs.
+    // Non-NULL only where the step may be taken: the problem has loadings and NO observation variances (d_obsvar == NULL, not
+    // merely zeros), the kernel found is the (N, K) one, and MK_VARIANT_SMOOTHER16 is not 2
+    const double *obs;
+    long obs_bs, obs_ts;
+    const unsigned char *lr_take; // [R], with obs: 1 where at least 7 of 8 of the record's steps observe every series (full_records_kernel)
 };
 
 struct AdjointArgs {
@@ -183,6 +189,9 @@ hipError_t launch_standardize(long R, long T, int N, int time_major, const doubl
 hipError_t launch_mask(long count, const double *obs, const unsigned char *mask, double *out, hipStream_t s);
 hipError_t launch_pack(long RT, int N, const double *obs, double *observations, double *indices, long *count,
                        hipStream_t s);
+// take[r] = 1 where at least 7 of 8 of record r's T steps have all N cells finite; *any |= 1 if some record qualifies (zeroed by the caller)
+hipError_t launch_full_records(long R, long T, int N, long obs_bs, long obs_ts, const double *obs, unsigned char *take, int *any,
+                               hipStream_t s);
 // mk_factor.hip
 hipError_t launch_fa_corr(long R, long T, int N, int time_major, const double *obs, double *corr, hipStream_t s);
 hipError_t launch_fa_analyse(long B, int N, long maxfactors, const double *corr, double *eigval, long long *nfact,

@@ -1050,12 +1050,25 @@ struct RecordIO {
 
 // EPI: 0 = smoothed records only; 1 = + fused projection (sim_means / sim_vars, section f2); 2 = + state means and
 // VARIANCES (mk_outputs.flags & MK_OUT_VAR_ONLY: what get_state_means / get_state_variances / get_state consume)
-template <int N, int K, int G, int EPI, bool SYM>
+// LR (a.obs given: the model has no observation variances; full-square records without an epilogue, n <= 10): the rank-K
+// covariance step.  After the N scalar updates of a step at which EVERY series is observed, Pf Z^T = 0 (R = 0), so
+// Pf[t] = B C B^T with B = [-Gamma ; I_K], J = Pf Phi Pp^-1 = B J_f (J_f: the K factor rows of J) and
+//     J D J^T = (J D J_f^T) B^T = u B^T,   u = J (J_f D)^T  (n x K):
+// 2 n K broadcast multiply-adds for u and N K for u B^T (Sweeps<n>::lowrank, lowrank_apply) instead of the 2 n^2 of jd and vjt.
+// J itself -- factorisation, substitutions, the mean -- is untouched.  Whether step t is such a step is read off the
+// observations (the filter applies the update of every finite cell, whatever its innovation variance), PER MODEL: a
+// wavefront of four full models runs the low-rank products only, one of none the general ones only, a mixed one both, each
+// under the EXEC mask of its 16-lane groups -- what a model computes never depends on its neighbours.  A mixed wavefront pays
+// both forms, so a model takes the step only if at least 7 of 8 of ITS record's steps are full (a.lr_take, counted exactly by
+// full_records_kernel once per uploaded observation set); a launch in which no record qualifies runs the parent's kernel.
+template <int N, int K, int G, int EPI, bool SYM, bool LR = false>
 __global__ void __launch_bounds__(256) smoother_record_kernel(SmootherArgs a)
 {
     constexpr bool PROJ = (EPI == 1), VAR = (EPI == 2);
     constexpr int n = N + K;
     static_assert(n <= G, "state dimension must fit the lane group");
+    static_assert(!LR || (G == 16 && EPI == 0 && !SYM && Sweeps<n>::fused && K <= Sweeps<n>::lowrank_max_k),
+                  "the rank-K step exists for the fused 16-lane sweeps on full-square records without an epilogue");
     using Gp = Group<G>;
     constexpr int GPB = 256 / G;
     const int lane = threadIdx.x % G;
@@ -1101,9 +1114,11 @@ __global__ void __launch_bounds__(256) smoother_record_kernel(SmootherArgs a)
     const int jr = lane < N ? lane : N - 1;
     double gam[K], pscale = 1.0, poffset = 0.0;
     double *pM = nullptr, *pV = nullptr;
-    if constexpr (PROJ) {
+    if constexpr (PROJ || LR) {
 #pragma unroll
         for (int k = 0; k < K; ++k) gam[k] = a.loadings[(rec_id * N + jr) * K + k];
+    }
+    if constexpr (PROJ) {
         if (a.scale) pscale = a.scale[rec_id * N + jr];
         if (a.offset) poffset = a.offset[rec_id * N + jr];
         const long pidx = (inst * a.bs + (T - 1) * a.ts) * N + jr;
@@ -1117,13 +1132,60 @@ __global__ void __launch_bounds__(256) smoother_record_kernel(SmootherArgs a)
         sV = a.state_vars + sidx;
     }
 
+    // LR: lane j < N fetches cell j of its model's observations WITH the record of the same step (lanes >= N replicate cell
+    // N - 1); one ballot when the record is consumed tells which of the wavefront's models observed all N series there.
+    // A VGPR more can cost a resident wavefront, so the loop carries one value more than the parent's, the fetched word (the
+    // built kernels: 206 VGPRs for the parent's 206 at (8,2) and (7,3), 166 for 166 at (6,2), 128 for 126 at (5,1), 104 for
+    // 102 at (4,1), 88 for 86 at (3,1), 74 for 72 at (2,1), 60 for 58 at (1,1)): only the HIGH word of the cell is fetched
+    // (exponent all ones = NaN / inf = missing), through a wavefront-uniform base that walks back in time in
+    // SGPRs plus a 32-bit lane offset (the C ABI hands the observations over only where they span less than 4 GiB); that
+    // offset and the lane's K loadings wait in LDS slots of the lane's own (written here, read back by the same lane: no
+    // synchronisation); the flags are wavefront-uniform lane masks (SGPRs), expanded per lane where the products branch; and
+    // the lane index is formed where it is used (lane_now: the empty asm keeps it from being hoisted into a register)
+    __shared__ double lds_gam[LR ? 256 * K : 1];
+    __shared__ unsigned lds_ooff[LR ? 256 : 1];
+    long otoff = 0, ostepb = 0; // byte offset of the step being fetched (wavefront-uniform), bytes per step
+    unsigned ooff = 0;
+    int yhi = 0, wbase = 0;
+    unsigned long long full_c = 0, full_n = 0; // lanes of the models that observed every series: at the step being smoothed / fetched
+    unsigned long long lr_models = 0;          // lanes of the models that take the rank-K step at their full steps (below)
+    auto lane_now = [&]() __attribute__((always_inline)) {
+        unsigned z = 0;
+        asm volatile("" : "+v"(z));
+        return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, z));
+    };
+    if constexpr (LR) {
+        ostepb = a.obs_ts * N * (long)sizeof(double);
+        otoff = (T - 1) * ostepb;
+        wbase = __builtin_amdgcn_readfirstlane((int)(threadIdx.x & ~63u));
+#pragma unroll
+        for (int k = 0; k < K; ++k) lds_gam[k * 256 + threadIdx.x] = gam[k];
+        const unsigned mbase = (unsigned)(rec_id * a.obs_bs * N * (long)sizeof(double)) + 4u; // high word of the model's cell 0
+        lds_ooff[threadIdx.x] = mbase + (unsigned)jr * (unsigned)sizeof(double);
+        lr_models = __ballot(a.lr_take[rec_id] != 0); // the model's record is full at 7 of 8 of its steps or more
+    }
     // fetch helpers: issue the HBM loads of one step / turn them into (x_r, row r)
     auto issue = [&](double &xnext) __attribute__((always_inline)) {
         recF -= rstep;
         RIO::load_issue(recF, rmap, prer);
+        if constexpr (LR) {
+            otoff -= ostepb;
+            asm volatile("" : "+s"(otoff)); // stays a scalar: no per-lane pointer is strength-reduced out of the address
+            yhi = *reinterpret_cast<const int *>(reinterpret_cast<const char *>(a.obs) + otoff + ooff);
+        }
     };
     auto finish = [&](double &xv, double(&row)[n]) __attribute__((always_inline)) {
+        if constexpr (LR) ooff = lds_ooff[wbase + lane_now()]; // for the issue() that follows; rides with the row's LDS reads
         RIO::load_finish(imgL, prer, rmap, gw, r, xv, row);
+        if constexpr (LR) {
+            unsigned long long m = __ballot((yhi & 0x7ff00000) != 0x7ff00000); // finite cells; all 16 bits of a group: a full step
+            m &= m >> 1;
+            m &= m >> 2;
+            m &= m >> 4;
+            m &= m >> 8;
+            m &= 0x0001000100010001ull;
+            full_n = ((m << 16) - m) & lr_models;
+        }
     };
     // DEFER (records only, EPI = 0 -- the full-output path): the smoothed record of a step goes into the store image at
     // the END of its iteration and leaves it in the MIDDLE of the next one, and the next filtered record is transposed
@@ -1179,6 +1241,7 @@ __global__ void __launch_bounds__(256) smoother_record_kernel(SmootherArgs a)
     if (T >= 2) {
         issue(xfc);
         finish(xfc, Pfc);
+        full_c = full_n;
         if (T >= 3) issue(xfn);
     }
 
@@ -1301,7 +1364,21 @@ __global__ void __launch_bounds__(256) smoother_record_kernel(SmootherArgs a)
         // ---- smoothed covariance (:465-474): Ps[t] = Pf[t] + J (Ps[t+1] - Pp[t+1]) J^T ----
         double V[n]; // V = J D (row r):  V[c] += J[r][k] * D[k][c], D[k][:] broadcast from lane k
         if constexpr (G == 16) dpp_guard(D); // D is compiler-produced (build-time hazard check)
-        if constexpr (FUSED) {
+        if constexpr (LR) {
+            // Pf[t] has rank K where the model observed every series at t: u B^T in place of both products.  The branch is
+            // uniform within a model's lane group, so every DPP read stays inside the active lanes
+            const int ln = lane_now();
+            if ((full_c >> ln) & 1ull) {
+                double u[K], gl[K];
+#pragma unroll
+                for (int k = 0; k < K; ++k) gl[k] = lds_gam[k * 256 + wbase + ln];
+                Sweeps<n>::lowrank(u, D, z);
+                Sweeps<n>::lowrank_apply(Psn, u, gl);
+            } else {
+                Sweeps<n>::jd(V, D, z);
+                Sweeps<n>::vjt(Psn, z, V);
+            }
+        } else if constexpr (FUSED) {
             Sweeps<n>::jd(V, D, z);
         } else {
 #pragma unroll
@@ -1316,7 +1393,8 @@ __global__ void __launch_bounds__(256) smoother_record_kernel(SmootherArgs a)
             for (int c = 0; c < n; ++c) Psn[c] = Pfc[c];
         }
         // Ps[r][c] = Pf[r][c] + sum_k V[r][k] J[c][k], J[c][k] broadcast from lane c
-        if constexpr (FUSED) {
+        if constexpr (LR) { // both products are done, in the form the step calls for
+        } else if constexpr (FUSED) {
             Sweeps<n>::vjt(Psn, z, V);
         } else {
             sfor<0, n>(MK_LAMBDA(kc) {
@@ -1333,10 +1411,12 @@ __global__ void __launch_bounds__(256) smoother_record_kernel(SmootherArgs a)
         }
         store(xs, Psn);
         xfc = xf_next;
+        full_c = full_n;
     }
     if constexpr (DEFER)
         if (recS) RIO::emit(imgS, recS, rmap); // the record of step 0 (T = 1: of the only step)
     if (a.status && live && lane == 0 && pivot_flags(pivmin)) atomicOr(a.status + inst, pivot_flags(pivmin));
+
 }
 
 
@@ -2528,6 +2608,25 @@ static hipError_t launch_smoother_nk(const SmootherArgs &a, hipStream_t s)
                     else MK_LAUNCH_BLK(0, false);
                 }
 #undef MK_LAUNCH_BLK
+                return hipGetLastError();
+            }
+        }
+        // the rank-K covariance step: a.obs is set by the C ABI where it may be taken (full-square records, no epilogue).  The
+        // kernel takes up to two VGPRs more than its parent (none at (8,2) and (6,2)); at a shape where they cost a resident
+        // wavefront (the allocation granule decides: of the ahead-of-time list only (2,1), 72 -> 74 VGPRs, 7 -> 6 wavefronts
+        // per SIMD) the parent's code runs instead
+        if constexpr (G == 16 && Sweeps<n>::fused && K <= Sweeps<n>::lowrank_max_k) {
+            static const bool keeps_occupancy = [] {
+                int parent = 0, lowrank = 0;
+                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&parent, smoother_record_kernel<N, K, G, 0, false, false>, 256, 0) != hipSuccess ||
+                    hipOccupancyMaxActiveBlocksPerMultiprocessor(&lowrank, smoother_record_kernel<N, K, G, 0, false, true>, 256, 0) != hipSuccess) {
+                    (void)hipGetLastError();
+                    return false;
+                }
+                return lowrank > 0 && lowrank >= parent;
+            }();
+            if (a.rs > 0 && a.obs && epi == 0 && !a.sym && keeps_occupancy) {
+                hipLaunchKernelGGL((smoother_record_kernel<N, K, G, 0, false, true>), dim3(grid), dim3(256), 0, s, a);
                 return hipGetLastError();
             }
         }

@@ -97,7 +97,7 @@ class BatchedKalman:
             pass
 
     # ------------------------------------------------------------------ kernel variants (A/B measurements)
-    _VARIANTS = {"smoother16": (0, ("record", "blk")),
+    _VARIANTS = {"smoother16": (0, ("record", "blk", "record_general")),
                  "wide_smoother": (1, ("mfma", "v1", "mfma_unfolded")),
                  "wide_filter": (2, ("auto", "lane_per_state", "split")),
                  "single_record": (3, ("sparse", "stepwise")),
@@ -110,7 +110,8 @@ class BatchedKalman:
 
     def set_variant(self, which, name):
         """Choose between two equivalent kernels of a shape class (``mk_set_kernel_variant``): ``"smoother16"``:
-        ``"record"`` (default) | ``"blk"``; ``"wide_smoother"``: ``"mfma"`` (default) | ``"v1"`` (built for N + K <= 51) | ``"mfma_unfolded"``; ``"wide_filter"``: ``"auto"`` (default: the split
+        ``"record"`` (default) | ``"blk"`` | ``"record_general"`` (the record kernel without the rank-K covariance step of
+        fully observed steps); ``"wide_smoother"``: ``"mfma"`` (default) | ``"v1"`` (built for N + K <= 51) | ``"mfma_unfolded"``; ``"wide_filter"``: ``"auto"`` (default: the split
         layout for more than two models per SIMD, one state per lane below) | ``"lane_per_state"`` | ``"split"``; ``"tape_filter"``
         (the writer of the backward tape, N <= 32): ``"observable"`` (default: the filter in the observable basis) | ``"state"``.
         Every member is tested against the oracle; there is no environment switch."""

@@ -4,8 +4,12 @@ library in its own child process (METRAN_HIP_LIBRARY), interleaved over ROUNDS r
 (the clock ramp, ``scripts/probe.py kernels --ramp``), kernel ms from hipEvents, the summed -2 log L and a checksum of every output array so
 that a build that computes something else shows.  Name a library twice for the A/A spread.
 
-  python scripts/ab_c2.py ab/parent.so ab/parent.so ab/new.so [--rounds 3] [--steps 20] [--B 8192] [--T 1000] [--packed-sym]
-                          [--records filtered]
+  python scripts/ab_c2.py ab/parent.so ab/parent.so ab/new.so ab/new.so@general [--rounds 3] [--steps 20] [--B 8192] [--T 1000]
+                          [--packed-sym] [--records filtered] [--missing 0.05]
+
+``lib.so@general``: the same library with the record smoother's general covariance products at every step
+(``set_variant("smoother16", "record_general")``: no rank-K step) -- a route of its own in the table.
+``--missing F``: that fraction of the cells missing, so that wavefronts mix full and partly observed steps.
 
 ``--records filtered``: the filtered-record-only route (filter_kernel OUT = 3: ``simulate_smoothed`` on the records path).
 Unlike ab_libs.py this stops at the FIRST child that does not exit with 0 and starts nothing more on the GPU after it."""
@@ -20,9 +24,12 @@ sys.path.insert(0, ".")
 from metran_amd.engine import BatchedKalman
 from metran_amd.synthetic import make_dfm_batch_torch
 B, T, sym, filtered, steps = int(sys.argv[1]), int(sys.argv[2]), sys.argv[3] == "1", sys.argv[4] == "1", int(sys.argv[5])
+missing, route = float(sys.argv[6]), sys.argv[7]
 dev = torch.device("cuda", 0)
-d = make_dfm_batch_torch(B, 8, 2, T, seed=2000, device=dev, missing=0.0)
+d = make_dfm_batch_torch(B, 8, 2, T, seed=2000, device=dev, missing=missing)
 kf = BatchedKalman(0, layout="time_major", packed_sym=sym)
+if route == "general":
+    kf.set_variant("smoother16", "record_general")
 kf.projection_path = "records"
 kf.set_observations(d["obs"]).set_loadings(d["loadings"])
 if filtered:
@@ -56,18 +63,19 @@ def opt(name, default):
 
 
 def main():
-    libs = [a for a in sys.argv[1:] if a.endswith(".so")]
+    libs = [a for a in sys.argv[1:] if a.endswith((".so", ".so@general"))]
     rounds, steps, B, T = max(3, opt("--rounds", 3)), opt("--steps", 20), opt("--B", 4096), opt("--T", 1000)
-    sym, filtered = "--packed-sym" in sys.argv, opt("--records", "both") == "filtered"
-    print("ab_c2: B = %d, T = %d, %s records, %s, %d rounds of %d timed launches after 10 warm-up launches"
-          % (B, T, "packed-symmetric" if sym else "full-square", "filtered record only" if filtered else "all six outputs", rounds, steps),
-          flush=True)
+    sym, filtered, missing = "--packed-sym" in sys.argv, opt("--records", "both") == "filtered", opt("--missing", 0.0)
+    print("ab_c2: B = %d, T = %d, %s records, %s, %g of the cells missing, %d rounds of %d timed launches after 10 warm-up launches"
+          % (B, T, "packed-symmetric" if sym else "full-square", "filtered record only" if filtered else "all six outputs", missing, rounds,
+             steps), flush=True)
     times, sums = {}, {}
     for rnd in range(rounds):
         for pos, lib in enumerate(libs):
-            env = dict(os.environ, METRAN_HIP_LIBRARY=os.path.abspath(lib))
-            out = subprocess.run([sys.executable, "-c", CHILD, str(B), str(T), "1" if sym else "0", "1" if filtered else "0", str(steps)],
-                                 env=env, capture_output=True, text=True)
+            path, _, route = lib.partition("@")
+            env = dict(os.environ, METRAN_HIP_LIBRARY=os.path.abspath(path))
+            out = subprocess.run([sys.executable, "-c", CHILD, str(B), str(T), "1" if sym else "0", "1" if filtered else "0", str(steps),
+                                  str(missing), route or "default"], env=env, capture_output=True, text=True)
             line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
             if out.returncode != 0 or not line:
                 print("%s (position %d, round %d) FAILED with exit status %d; nothing more is started\n%s"

@@ -126,10 +126,10 @@ def main(argv):
             continue
         end = starts[k + 1][0] if k + 1 < len(starts) else len(lines)
         body = []
-        for l in lines[i + 1:end]:
-            body.append(l)
-            if "s_endpgm" in l:
+        for l in lines[i + 1:end]:   # the whole function: a kernel may end in more than one place (one s_endpgm per exit)
+            if l.startswith(".Lfunc_end"):
                 break
+            body.append(l)
         ndpp, errs = check_function(name, body)
         print("%-70s %4d DPP instructions, %d hazard(s)" % (name[:70], ndpp, len(errs)))
         total_err += errs

@@ -8,6 +8,11 @@ on other ports; their latency is what the partner wavefront hides or does not). 
 time; calibration against measured launches is printed by --calibrate.
 
     python scripts/cycle_model.py file.s kernel_substring [models steps]      (default 4096 models x 2000 steps, 1024 SIMDs)
+
+The record smoother with the rank-K covariance step (smoother_record_kernel<.., LR = true>) chooses the form of its two
+covariance products per model: hipcc places both forms BEHIND the loop's back branch, each entered by an s_cbranch_execnz under
+the EXEC mask of the models that take it.  Such a loop is priced three times: every model of the wavefront at a full step (the
+rank-K form only), none (the general products only), and a mixed wavefront (both, one after the other).
 """
 import collections
 import re
@@ -35,7 +40,26 @@ def main_loop(s, name):
             if best is None or span > best[0]:
                 best = (span, labels[m.group(1)], k)
     loop = body[best[1]:best[2]] if best else body
-    return drop_pivot_redo(loop)
+    return drop_pivot_redo(loop), masked_blocks(body, best) if best else []
+
+
+def masked_blocks(body, best):
+    """Blocks of the loop that stand behind its back branch and are entered under an EXEC mask from inside it:
+    [(form, lines)], form = "full" behind s_and_saveexec (the condition holds: the rank-K products), "general" behind
+    s_andn2_saveexec (the other lanes)."""
+    _, start, end = best
+    labels = {m.group(1): k for k, l in enumerate(body) for m in [re.match(r"^(\.LBB\d+_\d+):", l)] if m}
+    order = sorted(labels.values())
+    out = []
+    for k in range(start, end):
+        m = re.search(r"s_cbranch_execnz\s+(\.LBB\d+_\d+)", body[k])
+        if not m or labels.get(m.group(1), 0) <= end:
+            continue
+        prev = next((body[j] for j in range(k - 1, start, -1) if "saveexec" in body[j]), "")
+        a = labels[m.group(1)]
+        b = next((x for x in order if x > a), len(body))
+        out.append(("general" if "s_andn2_saveexec" in prev else "full", body[a:b]))
+    return out
 
 
 def drop_pivot_redo(loop):
@@ -102,20 +126,31 @@ def estimate(path, key):
     s = open(path).read()
     out = []
     for name in [m for m in re.findall(r"^(_Z\w+):", s, re.M) if key in m]:
-        c = collections.Counter()
-        nop = 0
-        for l in main_loop(s, name):
-            l = l.split(";")[0].strip()
-            if not l or l.startswith(".") or l.endswith(":"):
-                continue
-            op = l.split()[0]
-            k = classify(op, l)
-            c[k] += 1
-            if k == "nop":
-                nop += int(l.split()[1]) + 1
-        cycles = sum(COST[k] * v for k, v in c.items() if k in COST) + nop
-        out.append((name, c, nop, cycles))
+        loop, blocks = main_loop(s, name)
+        forms = [("", loop)]
+        if blocks:   # per-model choice of the products: all full / none full / mixed
+            full = [l for f, b in blocks if f == "full" for l in b]
+            gen = [l for f, b in blocks if f == "general" for l in b]
+            forms = [(" [every model at a full step]", loop + full), (" [no model at a full step]", loop + gen), (" [mixed wavefront]", loop + full + gen)]
+        for tag, lines in forms:
+            c, nop, cycles = price(lines)
+            out.append((name + tag, c, nop, cycles))
     return out
+
+
+def price(lines):
+    c = collections.Counter()
+    nop = 0
+    for l in lines:
+        l = l.split(";")[0].strip()
+        if not l or l.startswith(".") or l.endswith(":"):
+            continue
+        op = l.split()[0]
+        k = classify(op, l)
+        c[k] += 1
+        if k == "nop":
+            nop += int(l.split()[1]) + 1
+    return c, nop, sum(COST[k] * v for k, v in c.items() if k in COST) + nop
 
 
 if __name__ == "__main__":

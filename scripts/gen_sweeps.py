@@ -166,6 +166,74 @@ def gen_fused(n):
     return s
 
 
+LOWRANK_MAX_K = 5  # factors the rank-K covariance step is generated for (and 2n + 2K <= 30 operands)
+
+
+def lowrank_max_k(n):
+    return max(0, min(n - 1, LOWRANK_MAX_K, (30 - 2 * n) // 2))
+
+
+def lowrank_lines(n, K):
+    """u = J (J_f D)^T over SYMBOLIC registers (u[k], Vf[k] / the split chains of K = 1, D[j], z[j]): (text, written, DPP source).
+    K chains run interleaved; K = 1 splits its one chain of n into two (even / odd terms) and adds them.  The zeroing of u stands
+    BETWEEN the two products: with the other chains' last multiply-adds it gives Vf[k] its two wait states before the second
+    product reads it through DPP."""
+    N, out = n - K, []
+    if K == 1:
+        va, vb, ua, ub = "Vf[0]", "Vb", "u[0]", "ub"
+        out += [("v_mov_b64 {%s}, 0" % r, r, None) for r in (va, vb)]
+        out += [("v_fmac_f64_dpp {%s}, {z[%d]}, {D[%d]} row_newbcast:%d%s" % ((va, vb)[j % 2], j, j, N, DPP), (va, vb)[j % 2], "z[%d]" % j)
+                for j in range(n)]
+        out += [("v_add_f64 {%s}, {%s}, {%s}" % (va, va, vb), va, None)]
+        out += [("v_mov_b64 {%s}, 0" % r, r, None) for r in (ua, ub)]
+        out += [("v_fmac_f64_dpp {%s}, {%s}, {z[%d]} row_newbcast:%d%s" % ((ua, ub)[c % 2], va, c, c, DPP), (ua, ub)[c % 2], va) for c in range(n)]
+        out += [("v_add_f64 {%s}, {%s}, {%s}" % (ua, ua, ub), ua, None)]
+        return out
+    out += [("v_mov_b64 {Vf[%d]}, 0" % k, "Vf[%d]" % k, None) for k in range(K)]
+    out += [("v_fmac_f64_dpp {Vf[%d]}, {z[%d]}, {D[%d]} row_newbcast:%d%s" % (k, j, j, N + k, DPP), "Vf[%d]" % k, "z[%d]" % j)
+            for j in range(n) for k in range(K)]
+    out += [("v_mov_b64 {u[%d]}, 0" % k, "u[%d]" % k, None) for k in range(K)]
+    out += [("v_fmac_f64_dpp {u[%d]}, {Vf[%d]}, {z[%d]} row_newbcast:%d%s" % (k, k, c, c, DPP), "u[%d]" % k, "Vf[%d]" % k)
+            for c in range(n) for k in range(K)]
+    return out
+
+
+def gen_lowrank(n):
+    """Sweeps<n>::lowrank / lowrank_apply, one overload per factor count K (N = n - K): the covariance step of a time step at
+    which every series is observed and R = 0, where Pf = B C B^T with B = [-Gamma ; I_K] and so J D J^T = u B^T."""
+    s = "    static constexpr int lowrank_max_k = %d; // rank-K covariance step: overloads for K = 1 .. this\n" % lowrank_max_k(n)
+    for K in range(1, lowrank_max_k(n) + 1):
+        N = n - K
+        lines, age = [], {}
+        for ln in lowrank_lines(n, K):  # a DPP source written inside the statement is two wait states old: pad where it is not
+            need = 2 - age.get(ln[2], 99) if ln[2] else 0
+            if need > 0:
+                lines.append(("s_nop %d" % (need - 1), None, None))
+            age = {r: a_ + max(need, 0) + 1 for r, a_ in age.items()}
+            age[ln[1]] = 0
+            lines.append(ln)
+        tmps = ["Vf[0]", "Vb", "ub"] if K == 1 else ["Vf[%d]" % k for k in range(K)]
+        regs = ["u[%d]" % k for k in range(K)] + tmps + ["D[%d]" % c for c in range(n)] + ["z[%d]" % c for c in range(n)]
+        idx = {r: "%%%d" % i for i, r in enumerate(regs)}
+        text = [ln[0] for ln in lines]
+        for r in sorted(idx, key=len, reverse=True):
+            text = [t.replace("{%s}" % r, idx[r]) for t in text]
+        s += "    // N = %d, K = %d: u = J (J_f D)^T (row r), J_f = rows %d.. of J.  Vf[k] of lane c = sum_j D[c][j] J[%d+k][j], then\n" % (N, K, N, N)
+        s += "    // u[k] = sum_c J[r][c] Vf[k] of lane c\n"
+        s += "    static __device__ __forceinline__ void lowrank(double (&u)[%d], const double (&D)[%d], const double (&z)[%d])\n    {\n" % (K, n, n)
+        s += "        double Vf[%d]%s;\n" % (K, ", Vb, ub" if K == 1 else "")
+        s += stmt(text, ['"=&v"(%s)' % r for r in regs[:K + len(tmps)]], ['"v"(%s)' % r for r in regs[K + len(tmps):]])
+        s += "    }\n"
+        # P[c] -= u[k] Gamma[c][k] (Gamma[c][k] = gam[k] of lane c < N), P[N+k] += u[k]     (operands: P 0..n-1, u, gam)
+        text = ["v_fmac_f64_dpp %%%d, %%%d, -%%%d row_newbcast:%d%s" % (c, n + K + k, n + k, c, DPP) for k in range(K) for c in range(N)]
+        text += ["v_add_f64 %%%d, %%%d, %%%d" % (N + k, N + k, n + k) for k in range(K)]
+        s += "    // Ps[r][:] = Pf[r][:] + (u B^T)[r][:]: P[c] -= u[k] Gamma[c][k], Gamma[c][k] = gam[k] broadcast from lane c < %d; P[%d+k] += u[k]\n" % (N, N)
+        s += "    static __device__ __forceinline__ void lowrank_apply(double (&P)[%d], const double (&u)[%d], const double (&gam)[%d])\n    {\n" % (n, K, K)
+        s += stmt(text, ['"+v"(P[%d])' % c for c in range(n)], ['"v"(u[%d])' % k for k in range(K)] + ['"v"(gam[%d])' % k for k in range(K)])
+        s += "    }\n"
+    return s
+
+
 def gen(n):
     s = "template <>\nstruct Sweeps<%d> {\n    static constexpr bool fused = true;\n" % n
     # forward substitution: z[c] -= bcast_c(A[k]) z[k], k = 0..n-2, c = k+1..n-1     (operands: z 0..n-1, A n..2n-2)
@@ -204,7 +272,7 @@ def gen(n):
         for k in ks:
             ins += ['"v"(z[%d])' % k, '"v"(V[%d])' % k]
         s += stmt(lines, ['"+v"(P[%d])' % c for c in range(n)], ins)
-    s += "    }\n" + gen_fused(n) + "};\n\n"
+    s += "    }\n" + gen_fused(n) + gen_lowrank(n) + "};\n\n"
     return s
 
 
@@ -214,7 +282,7 @@ def blocks(n, size):
 
 def gen_tiled(n):
     """11 <= n <= 16: the same five sweeps, each as a short sequence of <= 30-operand statements."""
-    s = "template <>\nstruct Sweeps<%d> {\n    static constexpr bool fused = true;\n    static constexpr bool fused_factor = false; // tiled shapes: ldlt_factor, then forward\n" % n
+    s = "template <>\nstruct Sweeps<%d> {\n    static constexpr bool fused = true;\n    static constexpr bool fused_factor = false; // tiled shapes: ldlt_factor, then forward\n    static constexpr int lowrank_max_k = 0;\n" % n
     KB = blocks(n, 7)
 
     def tri(forward):
@@ -298,7 +366,7 @@ def render():
          "// the two wait states between their producers and the statement (dpp_guard), scripts/check_dpp_hazards.py checks.\n"
          "#pragma once\n\n"
          "template <int n>\nstruct Sweeps {\n    static constexpr bool fused = false; // wider groups: the per-FMA primitives of Group<16>\n"
-         "    static constexpr bool fused_factor = false;\n};\n\n")
+         "    static constexpr bool fused_factor = false;\n    static constexpr int lowrank_max_k = 0; // no rank-K covariance step\n};\n\n")
     for n in range(2, 11):
         h += gen(n)
     h += ("// 11 <= n <= 16: a statement takes at most 30 operands -- every sweep is tiled into a few statements (blocks of 7\n"
