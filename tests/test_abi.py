@@ -138,19 +138,15 @@ def test_shape_module_builds_and_passes_hazard_check(tmp_path, monkeypatch):
 
 def test_generated_sweeps_header_is_current():
     """metran_amd/csrc/mk_sweeps.h is generated (scripts/gen_sweeps.py) and committed: the committed file must be what
-    the generator writes, and every statement must respect the 30-operand limit of an asm statement ("+v" counts twice)."""
-    import importlib.util
-    import re
+    the generator writes, every statement must respect the 30-operand limit of an asm statement ("+v" counts twice; the
+    reader of tests/sweeps_header.py asserts it per statement), and the rank-K overloads are those the operand limit allows."""
+    import sweeps_header
 
-    spec = importlib.util.spec_from_file_location("gen_sweeps", os.path.join(ROOT, "scripts", "gen_sweeps.py"))
-    gen = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(gen)
+    gen = sweeps_header.generator()
     text = gen.render()
     assert open(os.path.join(ROOT, "metran_amd", "csrc", "mk_sweeps.h")).read() == text
-    for stmt in re.findall(r"asm volatile\((.*?)\);", text, flags=re.S):
-        outs, ins = stmt.split("\n            : ")[1:3] if stmt.count("\n            : ") >= 2 else (stmt.split("\n            : ")[1], "")
-        n_ops = 2 * outs.count('"+v"') + outs.count('"=&v"') + ins.count('"v"')
-        assert 0 < n_ops <= 30, (n_ops, stmt[:120])
+    assert len(sweeps_header.statements(text=text)) == text.count("asm volatile(") > 0
+    assert [gen.lowrank_max_k(n) for n in range(2, 11)] == [max(0, min(n - 1, 5, (30 - 2 * n) // 2)) for n in range(2, 11)]
 
 
 def test_kernel_sources_read_no_environment_variable():
