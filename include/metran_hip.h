@@ -600,6 +600,62 @@ MK_API int64_t mk_weights_work_stride(int64_t N, int64_t K);
 MK_API int mk_observation_weights(mk_context *ctx, const mk_problem *prob, double *d_work, int time_major,
                                   const mk_weights_request *req, uint32_t *d_status);
 
+/* INTERVENTION EFFECTS by GLS (de Jong 1991, Ann. Statist. 19:1073-1083; Durbin & Koopman 2012, section 6.2; statsmodels'
+ * mle_regression, KFAS regression effects): level shifts, outliers and trends of single series as KNOWN regressors of the
+ * observation equation, y_t = X_t beta + Z x_t + e_t, estimated for fixed parameters.  Model and filter order as in
+ * mk_innovations; d_{t,j} and rf_{t,j} = 1 / f_{t,j} of every scalar update as in mk_observation_weights (zero at a cell that is
+ * not observed).
+ *   EFFECTS.  d_effects [n_records,M,4] = (series j, kind, t0, t1) as 64-bit integers, 0 <= t0 < t1 <= T; instance i uses the M
+ * effects of record i % n_records; a negative series marks an unused slot.  The regressor acts on series j alone:
+ *     MK_EFFECT_LEVEL  x_t = 1 for t0 <= t < t1, else 0 (a pulse is t1 = t0 + 1, a permanent shift t1 = T);
+ *     MK_EFFECT_RAMP   x_t = min(t, t1 - 1) - t0 + 1 for t >= t0, else 0 (one unit per step, held after t1 - 1).
+ *   REPLAY.  The covariance recursion does not depend on the data, so the filter's mean recursion of any data column is
+ *     a = x0 (column 0: y) or 0 (columns 1 .. M: the regressors);  per step a <- phi o a;  per cell j ascending
+ *     V = col[t,j] - z_j a,  a <- a + (d_{t,j} rf_{t,j}) V,
+ * with col = y (0 where it is not observed) or x_m on its series, 0 elsewhere.  Over the cells of the steps t >= t_first, in time
+ * order,  A[p,q] = sum (V_p rf) V_q  for q <= p, mirrored (d_normal [B,M+1,M+1]): A[0,0] is the filter's sum of sigmas, s = A[0,1:],
+ * S = A[1:,1:], and -2 log L(beta) = -2 log L(0) - 2 s'beta + beta'S beta exactly.  d_support [B,M] (int64) counts per effect the
+ * counted observed cells with x != 0.
+ *   SOLVE, in a fixed order: S scaled to unit diagonal; Cholesky in effect order; an effect with support 0 (or in an unused
+ * slot), or whose pivot in the scaled matrix is below 1e-12, is DROPPED and the others are solved without it.  d_beta [B,M] =
+ * S^-1 s, d_cov [B,M,M] = S^-1, d_gain [B] = s'S^-1 s = -2 log L(0) - -2 log L(beta); a dropped effect has a NaN beta, NaN in its row
+ * and column of d_cov and its bit (1 << m) in d_dropped [B] (uint32).  With t_first = T nothing is counted: every effect is
+ * dropped and the gain is 0.
+ *   Launches: as mk_observation_weights -- the recording forward pass into d_work (n_instances * T *
+ * mk_regression_work_stride(N, K) doubles = the weights stride: records, then the gain tape), the clear of the tape,
+ * innov_step_kernel -- then regress_replay_kernel (one instance per lane group, lane = state; the regressors are generated from
+ * the descriptors), the three timed in the smoother slot of mk_last_kernel_ms / mk_kernel_ms_totals.  Every sum has a fixed
+ * order: an instance's outputs are bit-identical whatever the batch, the layout of d_work or the neighbouring instances, and
+ * the block of A of a subset of the effects does not depend on the other effects of the call.  prob->warmup is ignored (t_first
+ * says which steps count); d_status (may be NULL) receives the filter's MK_FLAG_* bits -- the outputs of an instance with
+ * MK_FLAG_NONPOSITIVE_F are not meaningful.
+ *   mk_regression_adjust writes d_obs_out = d_obs_in - sum_m beta_m x_m for R records [R,T,N] (stored [T,R,N] when time_major
+ * is set; in place when the two pointers are equal), d_beta [R,M]: a NaN beta counts as 0, a NaN observation stays NaN.
+ *   Served: every supported shape with N + K <= 64, under either kernel family; mk_regression_work_stride returns 0 otherwise
+ * and mk_regression fails with MK_ERR_SHAPE.  MK_ERR_INVALID (no launch): a missing pointer (all of the request's are
+ * required), n_effects outside 1 .. mk_regression_max_effects() = 16, t_first < 0, a buffer larger than the allocation it
+ * points into, and -- after one small copy of the effects to the host -- a slot in use with series >= N, an unknown kind or
+ * t0 / t1 outside 0 <= t0 < t1 <= T. */
+#define MK_EFFECT_LEVEL 0
+#define MK_EFFECT_RAMP 1
+typedef struct mk_regression_request {
+    int64_t n_effects;            /* M per record, 1 .. mk_regression_max_effects() */
+    int64_t t_first;              /* the steps t >= t_first are counted (1: as Metran's warm-up) */
+    const int64_t *d_effects;     /* [n_records, M, 4] = (series, kind, t0, t1) */
+    double *d_beta;               /* [B, M] */
+    double *d_cov;                /* [B, M, M] */
+    double *d_gain;               /* [B] */
+    double *d_normal;             /* [B, M + 1, M + 1] */
+    int64_t *d_support;           /* [B, M] */
+    uint32_t *d_dropped;          /* [B] */
+} mk_regression_request;
+MK_API int64_t mk_regression_max_effects(void);
+MK_API int64_t mk_regression_work_stride(int64_t N, int64_t K);
+MK_API int mk_regression(mk_context *ctx, const mk_problem *prob, double *d_work, int time_major,
+                         const mk_regression_request *req, uint32_t *d_status);
+MK_API int mk_regression_adjust(mk_context *ctx, int64_t R, int64_t T, int64_t N, int time_major, int64_t n_effects,
+                                const int64_t *d_effects, const double *d_beta, const double *d_obs_in, double *d_obs_out);
+
 /* kalmansmoother for B instances (kalmanfilter.py:403-476).  Reads out->d_F and out->d_Pf
  * (as written by mk_filter); predicted moments are recomputed from them (Phi diagonal), so
  * d_Xp/d_Pp are not read.  Writes d_S, d_Ps (either may be NULL), d_status.  d_status is OVERWRITTEN (cleared on the context's

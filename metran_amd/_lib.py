@@ -8,7 +8,7 @@ import ctypes
 import os
 from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
 
-__all__ = ["MetranHipError", "lib", "library_path", "Problem", "Outputs", "ForecastRequest", "WeightsRequest", "check", "API"]
+__all__ = ["MetranHipError", "lib", "library_path", "Problem", "Outputs", "ForecastRequest", "WeightsRequest", "RegressionRequest", "check", "API"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIBNAME = "libmetran_hip.so"
@@ -99,6 +99,22 @@ class WeightsRequest(Structure):
     ]
 
 
+class RegressionRequest(Structure):
+    """``mk_regression_request`` (include/metran_hip.h)."""
+
+    _fields_ = [
+        ("n_effects", c_int64),
+        ("t_first", c_int64),
+        ("d_effects", c_void_p),
+        ("d_beta", c_void_p),
+        ("d_cov", c_void_p),
+        ("d_gain", c_void_p),
+        ("d_normal", c_void_p),
+        ("d_support", c_void_p),
+        ("d_dropped", c_void_p),
+    ]
+
+
 # name -> (restype, argtypes); this table is what tests check against the header.
 API = {
     "mk_abi_version": (c_int, []),
@@ -170,6 +186,10 @@ API = {
     "mk_forecast": (c_int, [c_void_p, POINTER(Problem), c_void_p, c_int, POINTER(ForecastRequest), c_void_p]),
     "mk_weights_work_stride": (c_int64, [c_int64, c_int64]),
     "mk_observation_weights": (c_int, [c_void_p, POINTER(Problem), c_void_p, c_int, POINTER(WeightsRequest), c_void_p]),
+    "mk_regression_max_effects": (c_int64, []),
+    "mk_regression_work_stride": (c_int64, [c_int64, c_int64]),
+    "mk_regression": (c_int, [c_void_p, POINTER(Problem), c_void_p, c_int, POINTER(RegressionRequest), c_void_p]),
+    "mk_regression_adjust": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mk_draw_perturb": (c_int, [c_void_p, POINTER(Problem), c_uint64, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p,
                                 c_void_p]),
     "mk_draw_combine": (c_int, [c_void_p, POINTER(Problem), c_int64, c_int, c_int, c_void_p, c_void_p]),

@@ -15,6 +15,8 @@ number comes from the HIP kernels:
                                  forecast_skill)
     observation_weights      ->  which observations a smoothed value comes from (get_observation_weights, get_state_weights,
                                  get_weight_shares)
+    regression               ->  intervention effects by GLS: level shifts, outliers and trends of single series
+                                 (fit_interventions, adjust_observations)
     draw_smoothed            ->  posterior draws of series and states (get_simulation_draws, get_state_draws)
     draw_window_statistics   ->  window statistics of the draws, reduced on the device (get_window_statistics)
 
@@ -23,8 +25,8 @@ table (``_KINDS``): ``_cache[kind] = (parameter set, {request: kept result})``. 
 parameter set -- different kinds may hold different ones -- and of that result only the keys its accessors read (the table's
 keep-list: never the forward pass's workspace, the records or the tape, which are hundreds of times the outputs), plus what
 the accessors derive from them once (``("simf", standardized)``, ``("decomp", standardized)``).  The kinds with a request
-(``forecast``, ``weights``) keep every request of their parameter set; another parameter set drops them all.  ``solve``,
-``mask_observations`` and ``unmask_observations`` clear the cache.  So asking for another series, the variances after the
+(``forecast``, ``weights``, ``regress``) keep every request of their parameter set; another parameter set drops them all.  ``solve``,
+``mask_observations``, ``unmask_observations``, ``adjust_observations`` and ``unadjust_observations`` clear the cache.  So asking for another series, the variances after the
 means, or the decomposition after the simulation does not launch anything.  The draws and their window statistics are not
 cached: an ensemble is the size of the thing it summarises.
 
@@ -58,6 +60,14 @@ def _weights(mb, phi, q, request):
     return mb.kf.subset([r]).observation_weights(phi[r:r + 1], q[r:r + 1], targets, what=what)
 
 
+def _regress(mb, phi, q, request):
+    """request = (effect table as nested tuples [R][M][4], t_first); beside the regression the objective it is the drop of:
+    -2 log L of the records as they are, counted from the same step."""
+    effects, t_first = request
+    out = mb.kf.regression(phi, q, np.asarray(effects, dtype=np.int64).reshape(mb.R, -1, 4), t_first=t_first)
+    return dict(out, obj=mb.kf.loglik(phi, q, warmup=t_first))
+
+
 # kind -> (engine call (facade, phi, q, request), whether the scaling is set first, keys of the result that are kept).
 # The scaling is set where the call writes ORIGINAL units: the projection, the leave-one-out predictions, the one- and
 # multi-step-ahead forecasts.  "q" is the q the run was computed for.
@@ -73,6 +83,12 @@ _KINDS = {
     "dist": (lambda mb, phi, q, _: mb.kf.disturbances(phi, q), False, ("r", "ninfo", "q")),
     "forecast": (_forecast, True, ("fan_mean", "fan_var", "track_mean", "track_var", "skill")),
     "weights": (_weights, False, ("weights", "intercept")),
+}
+# The kinds that ESTIMATE something from the records instead of reading the filter's or the smoother's output: the same three
+# columns, the same cache and the same way through ``MetranBatch._run``; a table of their own because ``_KINDS`` is the list of
+# the views of one smoothing pass that tests/test_batch_facade_host.py states.  Standardised units: the facade scales the estimates.
+_FIT_KINDS = {
+    "regress": (_regress, False, ("beta", "cov", "gain", "normal", "support", "dropped", "obj")),
 }
 
 
@@ -218,12 +234,12 @@ class MetranBatch:
 
     # ------------------------------------------------------------------ cached kernel runs (Metran._run_kalman)
     def _run(self, kind, alpha, request=None):
-        """The result of ``_KINDS[kind]`` for the parameter set and the (hashable) ``request``: from the cache, or from the engine
+        """The result of ``_KINDS[kind]`` (or ``_FIT_KINDS[kind]``) for the parameter set and the (hashable) ``request``: from the cache, or from the engine
         and then kept -- the keys of the kind's keep-list, nothing else.  A kind holds the results of one parameter set
         (metran.py:978-989 keeps one too); another parameter set replaces them once its own run has passed the status check."""
         import torch
 
-        call, scaling, keep = _KINDS[kind]
+        call, scaling, keep = _KINDS[kind] if kind in _KINDS else _FIT_KINDS[kind]
         a = self._alpha(alpha)
         hit = self._cache.get(kind)
         if hit is None or hit[0].shape != a.shape or not bool(torch.equal(hit[0], a)):
@@ -570,6 +586,99 @@ class MetranBatch:
         stamp = lambda v, k: index[int(v[k])] if v[4] > 0 else NaT  # noqa: E731
         return DataFrame({"sum_w": table[:, 0], "share": table[:, 1], "first": [stamp(v, 2) for v in table], "last": [stamp(v, 3) for v in table]},
                          index=MultiIndex.from_tuples(rows, names=["time", "series"]))
+
+    # ------------------------------------------------------------------ intervention effects (estimating what the screens found)
+    _EFFECT_KINDS = {"level": 0, "ramp": 1}
+
+    def _effect_step(self, r, when, end=False):
+        """A start (or exclusive end) of an intervention as a step of model ``r``: a timestamp on its index or an integer step;
+        an end may also be the model's length."""
+        L = int(self.batch.lengths[r])
+        if end and when is None:
+            return L
+        if end and isinstance(when, (int, np.integer)) and int(when) == L:
+            return L
+        return self._target_steps(r, when)[0]
+
+    def fit_interventions(self, interventions, alpha=None, t_first=1, standardized=False):
+        """Estimate intervention effects by GLS, parameters held fixed (``BatchedKalman.regression``; de Jong's augmented
+        filter, what statsmodels' ``mle_regression``, KFAS regression effects and STAMP interventions do): what
+        ``get_deletion_residuals`` and ``screen_breaks`` find, estimated instead of masked.  ``interventions``: a list of
+        ``(model, series name, kind, start, end=None)`` -- kind ``"level"`` (the series reads a constant off between start and
+        end: a pulse for one step, a re-installed sensor for ``end=None``) or ``"ramp"`` (it drifts one unit per step from start
+        and holds after end: a change of trend for ``end=None``); start and end are timestamps on the model's index or integer
+        steps, end is exclusive, None = to the end of the record.  The steps ``t >= t_first`` count, as in ``get_mle``'s warm-up.
+
+        Returns a DataFrame with one row per effect, indexed (model, effect): ``series, kind, start, end`` (time stamps; end NaT
+        = the end of the record), ``n_obs`` (the observations the effect acts on), ``estimate`` and ``stderr`` in the series'
+        ORIGINAL units (per step for a ramp; ``standardized=True``: the units the filter runs in), ``t``, ``pvalue`` (two-sided
+        normal) and ``dropped`` (True, with NaN estimates, for an effect without observations or collinear with the ones before
+        it).  ``frame.attrs["models"]`` is a per-model frame with ``gain`` (the drop of -2 log L), ``df`` (effects kept),
+        ``pvalue`` (chi-square with df degrees of freedom), ``obj`` and ``obj_adjusted``.  The standardisation constants are
+        those of the RAW series: they are not re-estimated for the adjusted ones."""
+        from pandas import DataFrame, Index, MultiIndex, NaT
+        from scipy.stats import chi2, norm
+
+        t_first = int(t_first)
+        per_model = [[] for _ in range(self.R)]
+        for item in interventions:
+            model, name, kind, start = item[:4]
+            end = item[4] if len(item) > 4 else None
+            r = int(model) - self.shard[0]
+            if not 0 <= r < self.R:
+                raise IndexError("model %s is not one of this batch" % (model,))
+            if kind not in self._EFFECT_KINDS:
+                raise ValueError("kind must be 'level' or 'ramp'")
+            t0, t1 = self._effect_step(r, start), self._effect_step(r, end, end=True)
+            if not t0 < t1:
+                raise ValueError("an intervention must end after it starts (model %s, series %s)" % (model, name))
+            per_model[r].append((self._series(r, name), self._EFFECT_KINDS[kind], t0, t1))
+        M = max(len(e) for e in per_model) if per_model else 0
+        if M < 1:
+            raise ValueError("interventions must name at least one effect")
+        table = tuple(tuple(e + [(-1, 0, 0, 1)] * (M - len(e))) for e in per_model)   # unused slots for the models with fewer
+        out = self._run("regress", alpha, (table, t_first))
+        beta, cov = out["beta"].cpu().numpy(), out["cov"].cpu().numpy()
+        support, dropped = out["support"].cpu().numpy(), out["dropped"].cpu().numpy()
+        gain, obj = out["gain"].cpu().numpy(), out["obj"].cpu().numpy()
+        std = self._std.cpu().numpy()
+        rows, labels = [], []
+        for r, effects in enumerate(per_model):
+            index = self.batch.index[r]
+            for m, (j, kind, t0, t1) in enumerate(effects):
+                scale = 1.0 if standardized else std[r, j]
+                gone = bool((int(dropped[r]) >> m) & 1)
+                est, se = beta[r, m] * scale, np.sqrt(cov[r, m, m]) * scale
+                tval = est / se
+                labels.append((r + self.shard[0], m))
+                rows.append({"series": self.batch.names[r][j], "kind": "level" if kind == 0 else "ramp", "start": index[t0],
+                             "end": index[t1] if t1 < len(index) else NaT, "n_obs": int(support[r, m]), "estimate": est, "stderr": se,
+                             "t": tval, "pvalue": 2.0 * norm.sf(abs(tval)), "dropped": gone})
+        frame = DataFrame(rows, index=MultiIndex.from_tuples(labels, names=["model", "effect"]))
+        df = np.array([sum(1 for m in range(len(e)) if not (int(dropped[r]) >> m) & 1) for r, e in enumerate(per_model)])
+        frame.attrs["models"] = DataFrame({"gain": gain, "df": df, "pvalue": np.where(df > 0, chi2.sf(gain, np.maximum(df, 1)), np.nan),
+                                           "obj": obj, "obj_adjusted": obj - gain},
+                                          index=Index(np.arange(self.R) + self.shard[0], name="model"))
+        frame.attrs["effects"] = np.asarray(table, dtype=np.int64).reshape(self.R, M, 4)
+        frame.attrs["beta"] = beta.copy()                  # standardised units: what adjust_observations subtracts
+        self.interventions = frame
+        return frame
+
+    def adjust_observations(self, table=None):
+        """Subtract fitted intervention effects from the records (``table``: a frame of ``fit_interventions``; None = the last
+        fit): afterwards ``get_simulation``, ``screen_breaks``, ``test_whiteness`` and ``solve`` run on the adjusted records.  A
+        dropped effect subtracts nothing.  A second call starts again from the original records; ``unadjust_observations``
+        reverts.  The series' standardisation constants stay those of the raw series."""
+        table = getattr(self, "interventions", None) if table is None else table
+        if table is None or "effects" not in getattr(table, "attrs", {}):
+            raise ValueError("no fitted interventions: call fit_interventions first or pass its frame")
+        self.kf.adjust_observations(table.attrs["effects"], table.attrs["beta"])
+        self._cache.clear()
+
+    def unadjust_observations(self):
+        """The records as they were before ``adjust_observations``."""
+        self.kf.unadjust_observations()
+        self._cache.clear()
 
     # ------------------------------------------------------------------ state disturbances (break detection)
     def get_state_disturbances(self, alpha=None):

@@ -19,6 +19,7 @@
 #include "mk_generic.h"
 #include "mk_internal.h"
 #include "mk_lbfgs.h"
+#include "regress_kernels.h"
 #include "weights_kernels.h"
 
 struct mk_context {
@@ -1673,6 +1674,139 @@ MK_API int mk_observation_weights(mk_context *ctx, const mk_problem *p, double *
     MK_HIP(mk::launch_innov_step(g, ctx->stream));
     MK_HIP(mk::launch_weights_walk(a, ctx->stream));
     MK_HIP(timing_stop(ctx, 1)); // reported in the smoother slot of mk_last_kernel_ms / mk_kernel_ms_totals
+    return MK_OK;
+}
+
+// ---- intervention effects by GLS (regress_kernels.hip) ----
+MK_API int64_t mk_regression_max_effects(void) { return mk::regress_max_effects; }
+
+MK_API int64_t mk_regression_work_stride(int64_t N, int64_t K)
+{
+    static_assert(mk::regress_max_states == mk::weights_max_states, "the regression runs on the weights' workspace");
+    return mk_weights_work_stride(N, K);
+}
+
+// the effects of a request, copied to the host: a slot in use must name a series, a kind and a step range that exist
+static int check_effects(mk_context *ctx, const char *who, const int64_t *d_effects, int64_t R, int64_t M, int64_t T, int64_t N)
+{
+    std::vector<int64_t> h((size_t)(R * M * 4));
+    MK_HIP(hipMemcpyAsync(h.data(), d_effects, sizeof(int64_t) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
+    MK_HIP(hipStreamSynchronize(ctx->stream));
+    for (int64_t i = 0; i < R * M; ++i) {
+        const int64_t *e = &h[(size_t)i * 4];
+        if (e[0] < 0) continue;
+        if (e[0] >= N)
+            return fail(MK_ERR_INVALID, "%s: d_effects[%lld, %lld]: series %lld is outside 0 .. N - 1 = %lld", who, (long long)(i / M),
+                        (long long)(i % M), (long long)e[0], (long long)(N - 1));
+        if (e[1] != MK_EFFECT_LEVEL && e[1] != MK_EFFECT_RAMP)
+            return fail(MK_ERR_INVALID, "%s: d_effects[%lld, %lld]: kind must be MK_EFFECT_LEVEL or MK_EFFECT_RAMP (got %lld)", who,
+                        (long long)(i / M), (long long)(i % M), (long long)e[1]);
+        if (!(0 <= e[2] && e[2] < e[3] && e[3] <= T))
+            return fail(MK_ERR_INVALID, "%s: d_effects[%lld, %lld]: need 0 <= t0 < t1 <= T = %lld (got t0 = %lld, t1 = %lld)", who,
+                        (long long)(i / M), (long long)(i % M), (long long)T, (long long)e[2], (long long)e[3]);
+    }
+    return MK_OK;
+}
+
+MK_API int mk_regression(mk_context *ctx, const mk_problem *p, double *d_work, int time_major, const mk_regression_request *req,
+                         uint32_t *d_status)
+{
+    MK_CTX(ctx);
+    // refused first: every other shape that mk_regression_work_stride does not serve is one check_problem refuses
+    if (p && p->N >= 1 && p->K >= 1 && p->N + p->K > mk::regress_max_states) return too_many_states("mk_regression", p, mk::regress_max_states);
+    if (int rc = check_problem(p)) return rc;
+    if (!req) return fail(MK_ERR_INVALID, "mk_regression: null mk_regression_request");
+    if (!d_work) return fail(MK_ERR_INVALID, "mk_regression: d_work is required");
+    if (!req->d_effects || !req->d_beta || !req->d_cov || !req->d_gain || !req->d_normal || !req->d_support || !req->d_dropped)
+        return fail(MK_ERR_INVALID, "mk_regression: d_effects, d_beta, d_cov, d_gain, d_normal, d_support and d_dropped are required");
+    if (req->n_effects < 1 || req->n_effects > mk::regress_max_effects)
+        return fail(MK_ERR_INVALID, "mk_regression: need 1 <= n_effects <= %d (got %lld)", mk::regress_max_effects, (long long)req->n_effects);
+    if (req->t_first < 0) return fail(MK_ERR_INVALID, "mk_regression: t_first must be >= 0");
+    if (!p->d_obs || !p->d_loadings) return fail(MK_ERR_INVALID, "d_obs and d_loadings are required");
+    const int64_t ws = mk_regression_work_stride(p->N, p->K);
+    if (!ws) return too_many_states("mk_regression", p, mk::regress_max_states);
+    const int64_t B = p->n_instances, M = req->n_effects, n = p->N + p->K;
+    const int64_t rs = mk::record_stride((int)n), gs = mk::weights_slot_stride(n);
+    static_assert(sizeof(int64_t) == sizeof(double), "buffers_fit counts 8-byte words");
+    const device_buffer bufs[8] = {{d_work, B * p->T * ws, "d_work (n_instances * T * mk_regression_work_stride(N, K) doubles)"},
+                                   {req->d_effects, p->n_records * M * 4, "d_effects (n_records * n_effects * 4 64-bit integers)"},
+                                   {req->d_beta, B * M, "d_beta (n_instances * n_effects doubles)"},
+                                   {req->d_cov, B * M * M, "d_cov (n_instances * n_effects^2 doubles)"},
+                                   {req->d_gain, B, "d_gain (n_instances doubles)"},
+                                   {req->d_normal, B * (M + 1) * (M + 1), "d_normal (n_instances * (n_effects + 1)^2 doubles)"},
+                                   {req->d_support, B * M, "d_support (n_instances * n_effects 64-bit integers)"},
+                                   {req->d_dropped, (B + 1) / 2, "d_dropped (n_instances 32-bit words)"}};
+    if (int rc = buffers_fit("mk_regression", bufs, 8)) return rc;
+    if (int rc = check_effects(ctx, "mk_regression", req->d_effects, p->n_records, M, p->T, p->N)) return rc;
+    // the records are packed at the head of d_work; the gain tape lives behind them
+    if (int rc = record_pass(ctx, p, d_work, rs, time_major, d_status)) return rc;
+    double *tape = d_work + B * p->T * rs;
+    mk::InnovArgs g;
+    memset(&g, 0, sizeof(g));
+    fill_model(g, p);
+    fill_initial(g, p);
+    fill_layout(g, time_major, B, p->T);
+    g.N = (int)p->N;
+    g.K = (int)p->K;
+    g.rs = rs;
+    g.F = d_work;
+    g.gain = tape;
+    g.gs = gs;
+    mk::RegressArgs a;
+    memset(&a, 0, sizeof(a));
+    fill_model(a, p);
+    fill_initial(a, p);
+    fill_layout(a, time_major, B, p->T);
+    a.N = (int)p->N;
+    a.K = (int)p->K;
+    a.M = M;
+    a.t_first = req->t_first;
+    a.gs = gs;
+    a.gain = tape;
+    a.effects = req->d_effects;
+    a.beta = req->d_beta;
+    a.cov = req->d_cov;
+    a.gainout = req->d_gain;
+    a.normal = req->d_normal;
+    a.support = req->d_support;
+    a.dropped = req->d_dropped;
+    MK_HIP(timing_start(ctx, 1));
+    // a cell that is not observed keeps an all-zero slot: innov_step_kernel writes the observed ones only
+    MK_HIP(hipMemsetAsync(tape, 0, sizeof(double) * (size_t)(B * p->T * p->N * gs), ctx->stream));
+    MK_HIP(mk::launch_innov_step(g, ctx->stream));
+    MK_HIP(mk::launch_regress_replay(a, ctx->stream));
+    MK_HIP(timing_stop(ctx, 1)); // reported in the smoother slot of mk_last_kernel_ms / mk_kernel_ms_totals
+    return MK_OK;
+}
+
+MK_API int mk_regression_adjust(mk_context *ctx, int64_t R, int64_t T, int64_t N, int time_major, int64_t n_effects,
+                                const int64_t *d_effects, const double *d_beta, const double *d_obs_in, double *d_obs_out)
+{
+    MK_CTX(ctx);
+    if (R < 1 || T < 1 || N < 1) return fail(MK_ERR_INVALID, "mk_regression_adjust: need R, T, N >= 1");
+    if (n_effects < 1 || n_effects > mk::regress_max_effects)
+        return fail(MK_ERR_INVALID, "mk_regression_adjust: need 1 <= n_effects <= %d (got %lld)", mk::regress_max_effects, (long long)n_effects);
+    if (!d_effects || !d_beta || !d_obs_in || !d_obs_out)
+        return fail(MK_ERR_INVALID, "mk_regression_adjust: d_effects, d_beta, d_obs_in and d_obs_out are required");
+    const device_buffer bufs[4] = {{d_effects, R * n_effects * 4, "d_effects (R * n_effects * 4 64-bit integers)"},
+                                   {d_beta, R * n_effects, "d_beta (R * n_effects doubles)"},
+                                   {d_obs_in, R * T * N, "d_obs_in (R * T * N doubles)"},
+                                   {d_obs_out, R * T * N, "d_obs_out (R * T * N doubles)"}};
+    if (int rc = buffers_fit("mk_regression_adjust", bufs, 4)) return rc;
+    if (int rc = check_effects(ctx, "mk_regression_adjust", d_effects, R, n_effects, T, N)) return rc;
+    mk::RegressAdjustArgs a;
+    memset(&a, 0, sizeof(a));
+    a.R = R;
+    a.T = T;
+    a.M = n_effects;
+    a.N = (int)N;
+    a.bs = time_major ? 1 : T;
+    a.ts = time_major ? R : 1;
+    a.effects = d_effects;
+    a.beta = d_beta;
+    a.in = d_obs_in;
+    a.out = d_obs_out;
+    MK_HIP(mk::launch_regress_adjust(a, ctx->stream));
     return MK_OK;
 }
 

@@ -14,7 +14,7 @@ import logging
 import numpy as np
 
 from . import _lib
-from ._lib import ForecastRequest, MetranHipError, Outputs, Problem, WeightsRequest, check
+from ._lib import ForecastRequest, MetranHipError, Outputs, Problem, RegressionRequest, WeightsRequest, check
 
 logger = logging.getLogger(__name__)
 
@@ -174,6 +174,7 @@ class BatchedKalman:
         obs = torch.where(obs == -1e10, torch.full_like(obs, float("nan")), obs)
         self.obs = self._layout(obs)
         self._obs_unmasked = None
+        self._obs_unadjusted = None
         self._grad_pending = self._grad_alpha = None  # a pending forward pass belongs to the previous dataset
         self.R, self.T, self.N = (int(s) for s in self.obs.shape)
         check(self._L.mk_observations_changed(self._ctx))  # a recycled allocation may carry a new record at an old address
@@ -198,7 +199,7 @@ class BatchedKalman:
         self._bind_stream()
         check(self._L.mk_standardize(self._ctx, self.R, self.T, self.N, int(self.time_major), self._p(self.obs),
                                      self._p(self.obs), self._p(mean), self._p(std)))
-        self._obs_unmasked = None
+        self._obs_unmasked = self._obs_unadjusted = None
         self.scale, self.offset = std, mean
         check(self._L.mk_observations_changed(self._ctx))  # standardised in place
         return mean, std
@@ -708,9 +709,9 @@ class BatchedKalman:
         return res
 
     # ------------------------------------------------------------------ the record readers: one scaffold
-    # loo_predict, disturbances, innovations, forecast and observation_weights run the recording forward pass into a workspace ("_work") and one kernel
+    # loo_predict, disturbances, innovations, forecast, observation_weights and regression run the recording forward pass into a workspace ("_work") and one kernel
     # that reads its filtered records.  NOTE: loo_supported() and disturbances_supported() are methods, innovations_supported and
-    # forecast_supported / observation_weights_supported properties -- an inconsistency of the public API that is kept.
+    # forecast_supported / observation_weights_supported / regression_supported properties -- an inconsistency of the public API that is kept.
     def _reader_stride(self, fn, specialised_only, refusal=None):
         """Doubles per (instance, step) of a record reader's workspace, the C ABI's ``fn(N, K)``; where the shape is not served
         0, or with ``refusal`` (a text with places for N and K) a MetranHipError."""
@@ -1029,6 +1030,130 @@ class BatchedKalman:
         self._mask_bad_instances(res, ("weights", "intercept"))
         return res
 
+    # ------------------------------------------------------------------ intervention effects by GLS
+    EFFECT_KINDS = {"level": 0, "ramp": 1}   # MK_EFFECT_LEVEL / MK_EFFECT_RAMP
+
+    @property
+    def regression_supported(self):
+        """True when ``regression`` serves this engine's shape (C ABI ``mk_regression_work_stride`` > 0): N + K <= 64,
+        specialised or size-generic kernels alike."""
+        return self._reader_stride(self._L.mk_regression_work_stride, False) > 0
+
+    def _regression_stride(self):
+        return self._reader_stride(self._L.mk_regression_work_stride, False,
+                                   "intervention effects serve shapes with N + K <= 64; (N=%s, K=%s) is not one")
+
+    def _regression_shapes(self, B, M):
+        """name -> (logical shape, follows the engine's layout) of the float64 buffers of ``regression``."""
+        shapes = self._bt_shapes(B, _work=self._regression_stride())
+        shapes.update(beta=((B, M), False), cov=((B, M, M), False), gain=((B,), False), normal=((B, M + 1, M + 1), False))
+        return shapes
+
+    def _effect_table(self, effects):
+        """``[R,M,4]`` int64 on the device from ``[R,M,4]`` or ``[M,4]`` (shared by the records)."""
+        torch = _torch()
+        ef = torch.as_tensor(effects, dtype=torch.int64)
+        if ef.ndim == 2:
+            ef = ef[None].expand(self.R, -1, -1)
+        mmax = int(self._L.mk_regression_max_effects())
+        if ef.ndim != 3 or ef.shape[0] != self.R or not 1 <= ef.shape[1] <= mmax or ef.shape[2] != 4:
+            raise ValueError("effects must be [%d,M,4] (or [M,4]) integers (series, kind, t0, t1), 1 <= M <= %d" % (self.R, mmax))
+        return ef.to(self.device).contiguous()
+
+    def alloc_regression(self, B, M):
+        """Buffers of ``regression`` for B instances and M effects per record (the forward pass's workspace with the gain tape +
+        the outputs), for callers that run it repeatedly (pass them back as ``buffers=``)."""
+        torch = _torch()
+        M = int(M)
+        if not 1 <= M <= int(self._L.mk_regression_max_effects()):
+            raise ValueError("M must be in 1..%d" % int(self._L.mk_regression_max_effects()))
+        res = self._reader_buffers(None, self._regression_shapes(B, M), "alloc_regression", sep=", ")
+        res["support"] = torch.empty((B, M), dtype=torch.int64, device=self.device)
+        res["dropped"] = torch.empty(B, dtype=torch.int32, device=self.device)
+        return res
+
+    def regression(self, phi, q, effects, t_first=1, x0=None, P0=None, buffers=None):
+        """INTERVENTION EFFECTS by GLS for B instances (C ABI ``mk_regression``; de Jong's augmented filter): level shifts,
+        outliers and trends of single series as known regressors of the observation equation, ``y_t = X_t beta + Z x_t + e_t``,
+        estimated for fixed parameters.  ``effects``: ``[R,M,4]`` integers ``(series, kind, t0, t1)`` (or ``[M,4]``, shared by
+        the records), ``0 <= t0 < t1 <= T``; kind 0 (``EFFECT_KINDS["level"]``): x = 1 on ``t0 <= t < t1``; kind 1 (``"ramp"``):
+        x = min(t, t1 - 1) - t0 + 1 from t0 on; a negative series marks an unused slot; instance b uses the effects of record
+        ``b % R``.  The cells of the steps ``t >= t_first`` are counted.  Returns a dict with ``beta [B,M]`` (in the units of the
+        standardised observations the filter runs on), ``cov [B,M,M]`` = Var beta, ``gain [B]`` (the drop of -2 log L at beta),
+        ``normal [B,M+1,M+1]`` (the augmented normal matrix A: A[0,0] the filter's sum of sigmas, A[0,1:] = s, A[1:,1:] = S),
+        ``support [B,M]`` (counted observed cells with x != 0), ``dropped [B]`` (bit m: effect m has support 0 or is collinear
+        with the effects before it; its beta and its row and column of cov are NaN, the others are solved without it) and
+        ``status`` (the filter's MK_FLAG_* bits); the rows of an instance whose status carries ``FLAG_NONPOSITIVE_F`` are NaN.
+        Four launches (the recording forward pass, a clear, the gain writer, the replay); an instance's outputs do not depend on
+        the batch, bit for bit."""
+        torch = _torch()
+        t_first = int(t_first)
+        if t_first < 0:
+            raise ValueError("t_first must be >= 0")
+        self._regression_stride()
+        ef = self._effect_table(effects)
+        M = int(ef.shape[1])
+        prob, keep, B = self._problem(phi, q, 0, x0, P0)
+        res = self._reader_buffers(buffers, self._regression_shapes(B, M), "alloc_regression", sep=", ")
+        for key, shape, dtype in (("support", (B, M), torch.int64), ("dropped", (B,), torch.int32)):
+            t = res.get(key)
+            if buffers is None:
+                t = res[key] = torch.empty(shape, dtype=dtype, device=self.device)
+            if t is None or tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous():
+                raise ValueError("buffers[%r] must be a contiguous %s tensor of shape %s (alloc_regression)" % (key, dtype, shape))
+        req = RegressionRequest()
+        req.n_effects, req.t_first, req.d_effects = M, t_first, ef.data_ptr()
+        for field, key in (("d_beta", "beta"), ("d_cov", "cov"), ("d_gain", "gain"), ("d_normal", "normal"), ("d_support", "support"),
+                           ("d_dropped", "dropped")):
+            setattr(req, field, res[key].data_ptr())
+        self._bind_stream()
+        check(self._L.mk_regression(self._ctx, ctypes.byref(prob), self._p(res["_work"]), 1 if self.time_major else 0,
+                                    ctypes.byref(req), self._p(res["status"])))
+        self._mask_bad_instances(res, ("beta", "cov", "gain", "normal"))
+        return res
+
+    def adjust_observations(self, effects, beta):
+        """Subtract fitted intervention effects from the observations (C ABI ``mk_regression_adjust``): ``obs - sum_m beta_m x_m``
+        with ``effects [R,M,4]`` as in ``regression`` and ``beta [R,M]`` in the units of the engine's observations (a NaN beta, a
+        dropped effect, counts as 0).  Applied to the current observations and, if a mask is active, to the kept unmasked copy
+        as well, so that ``unmask_observations`` afterwards gives adjusted, unmasked records.  The originals of both are kept:
+        ``unadjust_observations`` restores them (a mask set or lifted in between goes with it), and a second
+        ``adjust_observations`` starts again from them."""
+        torch = _torch()
+        if self.obs is None:
+            raise MetranHipError("call set_observations first")
+        ef = self._effect_table(effects)
+        M = int(ef.shape[1])
+        beta = self._dev(beta, (self.R, M), "beta")
+        kept = getattr(self, "_obs_unadjusted", None)
+        base, base_unmasked = kept if kept is not None else (self.obs, getattr(self, "_obs_unmasked", None))
+        self._bind_stream()
+
+        def adjusted(t):
+            if t is None:
+                return None
+            out = torch.empty_like(t)
+            check(self._L.mk_regression_adjust(self._ctx, self.R, self.T, self.N, 1 if self.time_major else 0, M, self._p(ef),
+                                               self._p(beta), self._p(t), self._p(out)))
+            return out
+
+        obs, unmasked = adjusted(base), adjusted(base_unmasked)
+        self._obs_unadjusted = (base, base_unmasked)
+        self.obs, self._obs_unmasked = obs, unmasked
+        self._grad_pending = self._grad_alpha = None  # a pending forward pass belongs to the records before
+        check(self._L.mk_observations_changed(self._ctx))
+        return self
+
+    def unadjust_observations(self):
+        """The observations as they were before ``adjust_observations`` (and the kept unmasked copy, if a mask was active)."""
+        kept = getattr(self, "_obs_unadjusted", None)
+        if kept is not None:
+            self.obs, self._obs_unmasked = kept
+            self._obs_unadjusted = None
+            self._grad_pending = self._grad_alpha = None
+            check(self._L.mk_observations_changed(self._ctx))
+        return self
+
     # ------------------------------------------------------------------ posterior draws (simulation smoother)
     def _draw_perturb(self, prob, B, ndraws, seed, first_instance, first_draw, antithetic, L0, want_zx, want_x):
         """``mk_draw_perturb`` for ``ndraws`` draws of the B instances of ``prob``: ``(ystar, zxplus or None, xplus or None)``,
@@ -1064,7 +1189,7 @@ class BatchedKalman:
         self.obs, self.R, self.T, self.N = obs, R, T, N
         self.loadings, self.K = loadings, int(loadings.shape[2])
         self.obsvar, self.scale, self.offset = obsvar, scale, offset
-        self._obs_unmasked = None
+        self._obs_unmasked = self._obs_unadjusted = None
         self._grad_pending = self._grad_alpha = None
         if (self.N, self.K) != shape_before:
             self._ensure_kernels()
