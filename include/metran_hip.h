@@ -656,6 +656,44 @@ MK_API int mk_regression(mk_context *ctx, const mk_problem *prob, double *d_work
 MK_API int mk_regression_adjust(mk_context *ctx, int64_t R, int64_t T, int64_t N, int time_major, int64_t n_effects,
                                 const int64_t *d_effects, const double *d_beta, const double *d_obs_in, double *d_obs_out);
 
+/* ---- exact window means, changes and contrasts of the smoothed signal (functional_kernels.hip) --------------------------------
+ * The posterior mean and variance of LINEAR functionals of the smoothed path, per instance b (record r = b % n_records), window w
+ * and contrast c:
+ *     l = sum_t alpha_t c'(scale o Z x_t + offset),     alpha_t = 1/(t1 - t0) on [t0, t1),   -1/(t3 - t2) on [t2, t3),
+ * (t0, t1, t2, t3) = d_windows[r, w], two half-open step ranges: with t2 == t3 the mean of the signal over a window, with t1 - t0 = 1 a
+ * point value, with both ranges "period A minus period B" (disjoint ranges in either order).  It is a functional of the SIGNAL Z x,
+ * as d_sim_means / d_sim_vars are: no observation variance is added; scale / offset are those of mk_problem (1 / 0 when NULL).  The
+ * posterior is Gaussian, mean = sum_t w_t' S_t + (sum_t alpha_t) c'offset and, with w_t = alpha_t Z'(c o scale),
+ *     var = sum_t w_t' Ps_t w_t + 2 sum_{t<s} w_t' J_t ... J_{s-1} Ps_s w_s,      J_t = Pf_t Phi Pp_{t+1}^-1,  Pp_{t+1} = Phi Pf_t Phi + Q,
+ * the second sum over the smoother's covariance ACROSS time, Cov(x_t, x_s | Y) = J_t ... J_{s-1} Ps_s (the smoothed state
+ * autocovariance: de Jong & Mackinnon 1988; Durbin & Koopman 2012, section 4.7; what statsmodels returns as smoothed_state_autocov),
+ * summed by one backward walk of the hull of the two ranges:  c_t = J_t u_{t+1},  p_t = Ps_t w_t,  var += w_t'(p_t + 2 c_t),
+ * u_t = p_t + c_t.  The [T,T,n,n] object is never formed.
+ *   mk_functionals_max_contrasts  64
+ *   mk_functionals_work_stride    doubles per (instance, step) of d_work (the filtered and the smoothed record); 0 where the route
+ *                                 does not serve the shape (N + K > 64)
+ *   mk_functionals                runs the recording forward pass and the smoother that mk_filter_smooth runs for the shape (full-square
+ *                                 records) into d_work, then one walk per (instance, window), the window's contrasts against one
+ *                                 factorisation of Pp_{t+1} per step.  d_mean, d_var [B, W, C].  d_contrasts [n_records, C, N], or NULL = the
+ *                                 N unit contrasts (n_contrasts must then be N).  Ranges are clamped to [0, T]; a functional whose first
+ *                                 range is empty is NaN in both outputs; a variance that rounding takes below zero is stored as zero.
+ *                                 Pivots of Pp_{t+1} as in the smoothers: a pivot <= 0 is dropped with MK_FLAG_RANK_DEFICIENT, < -1e-8 sets
+ *                                 MK_FLAG_NOT_SPD (ORed into d_status beside the filter's and the smoother's bits).  An instance's
+ *                                 results do not depend on the batch, on the other windows or on the other contrasts, bit for bit.
+ *                                 MK_ERR_INVALID: a missing pointer, n_windows < 1, n_contrasts outside 1 .. 64, a buffer larger than its
+ *                                 allocation; MK_ERR_SHAPE: N + K > 64 (packed-symmetric records are not served: the records are the
+ *                                 call's own, full-square). */
+typedef struct mk_functional_request {
+    int64_t n_windows;            /* W per record, >= 1 */
+    int64_t n_contrasts;          /* C per record, 1 .. mk_functionals_max_contrasts() */
+    const int64_t *d_windows;     /* [n_records, W, 4] = (t0, t1, t2, t3) */
+    const double *d_contrasts;    /* [n_records, C, N], or NULL: the N unit contrasts */
+} mk_functional_request;
+MK_API int64_t mk_functionals_max_contrasts(void);
+MK_API int64_t mk_functionals_work_stride(int64_t N, int64_t K);
+MK_API int mk_functionals(mk_context *ctx, const mk_problem *prob, double *d_work, int time_major,
+                          const mk_functional_request *req, double *d_mean, double *d_var, uint32_t *d_status);
+
 /* kalmansmoother for B instances (kalmanfilter.py:403-476).  Reads out->d_F and out->d_Pf
  * (as written by mk_filter); predicted moments are recomputed from them (Phi diagonal), so
  * d_Xp/d_Pp are not read.  Writes d_S, d_Ps (either may be NULL), d_status.  d_status is OVERWRITTEN (cleared on the context's

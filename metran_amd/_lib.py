@@ -115,6 +115,17 @@ class RegressionRequest(Structure):
     ]
 
 
+class FunctionalRequest(Structure):
+    """``mk_functional_request`` (include/metran_hip.h)."""
+
+    _fields_ = [
+        ("n_windows", c_int64),
+        ("n_contrasts", c_int64),
+        ("d_windows", c_void_p),
+        ("d_contrasts", c_void_p),
+    ]
+
+
 # name -> (restype, argtypes); this table is what tests check against the header.
 API = {
     "mk_abi_version": (c_int, []),
@@ -190,6 +201,9 @@ API = {
     "mk_regression_work_stride": (c_int64, [c_int64, c_int64]),
     "mk_regression": (c_int, [c_void_p, POINTER(Problem), c_void_p, c_int, POINTER(RegressionRequest), c_void_p]),
     "mk_regression_adjust": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mk_functionals_max_contrasts": (c_int64, []),
+    "mk_functionals_work_stride": (c_int64, [c_int64, c_int64]),
+    "mk_functionals": (c_int, [c_void_p, POINTER(Problem), c_void_p, c_int, POINTER(FunctionalRequest), c_void_p, c_void_p, c_void_p]),
     "mk_draw_perturb": (c_int, [c_void_p, POINTER(Problem), c_uint64, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p,
                                 c_void_p]),
     "mk_draw_combine": (c_int, [c_void_p, POINTER(Problem), c_int64, c_int, c_int, c_void_p, c_void_p]),

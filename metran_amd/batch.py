@@ -17,6 +17,8 @@ number comes from the HIP kernels:
                                  get_weight_shares)
     regression               ->  intervention effects by GLS: level shifts, outliers and trends of single series
                                  (fit_interventions, adjust_observations)
+    functionals              ->  exact window means, changes between periods and contrasts of series, from the smoother's
+                                 covariance across time (get_window_means, get_window_mean, get_changes)
     draw_smoothed            ->  posterior draws of series and states (get_simulation_draws, get_state_draws)
     draw_window_statistics   ->  window statistics of the draws, reduced on the device (get_window_statistics)
 
@@ -25,7 +27,7 @@ table (``_KINDS``): ``_cache[kind] = (parameter set, {request: kept result})``. 
 parameter set -- different kinds may hold different ones -- and of that result only the keys its accessors read (the table's
 keep-list: never the forward pass's workspace, the records or the tape, which are hundreds of times the outputs), plus what
 the accessors derive from them once (``("simf", standardized)``, ``("decomp", standardized)``).  The kinds with a request
-(``forecast``, ``weights``, ``regress``) keep every request of their parameter set; another parameter set drops them all.  ``solve``,
+(``forecast``, ``weights``, ``regress``, ``functionals``) keep every request of their parameter set; another parameter set drops them all.  ``solve``,
 ``mask_observations``, ``unmask_observations``, ``adjust_observations`` and ``unadjust_observations`` clear the cache.  So asking for another series, the variances after the
 means, or the decomposition after the simulation does not launch anything.  The draws and their window statistics are not
 cached: an ensemble is the size of the thing it summarises.
@@ -68,6 +70,18 @@ def _regress(mb, phi, q, request):
     return dict(out, obj=mb.kf.loglik(phi, q, warmup=t_first))
 
 
+def _functionals(mb, phi, q, request):
+    """request = (windows as nested tuples [R][W][4], contrasts as nested tuples [R][C][N] or None, standardized): the call sets
+    the scaling it is asked for itself (standardised units: none) and leaves the facade's behind."""
+    windows, contrasts, standardized = request
+    mb.kf.set_scaling(None, None) if standardized else mb.kf.set_scaling(mb._std, mb._mean)
+    try:
+        return mb.kf.functionals(phi, q, np.asarray(windows, dtype=np.int64).reshape(mb.R, -1, 4),
+                                 None if contrasts is None else np.asarray(contrasts, dtype=np.float64).reshape(mb.R, -1, mb.N))
+    finally:
+        mb.kf.set_scaling(mb._std, mb._mean)
+
+
 # kind -> (engine call (facade, phi, q, request), whether the scaling is set first, keys of the result that are kept).
 # The scaling is set where the call writes ORIGINAL units: the projection, the leave-one-out predictions, the one- and
 # multi-step-ahead forecasts.  "q" is the q the run was computed for.
@@ -89,6 +103,8 @@ _KINDS = {
 # the views of one smoothing pass that tests/test_batch_facade_host.py states.  Standardised units: the facade scales the estimates.
 _FIT_KINDS = {
     "regress": (_regress, False, ("beta", "cov", "gain", "normal", "support", "dropped", "obj")),
+    # exact moments of linear functionals of the smoothed signal, in the units the request names
+    "functionals": (_functionals, False, ("mean", "var")),
 }
 
 
@@ -829,6 +845,92 @@ class MetranBatch:
         self._series(r, name)
         frame = self.get_window_statistics(windows, thresholds, ndraws, probs, seed, alpha, antithetic)
         return frame.loc[(r + self.shard[0], name)]
+
+    # ------------------------------------------------------------------ exact window means, changes and contrasts
+    def _contrast_table(self, contrasts):
+        """``contrasts`` of ``get_window_means`` / ``get_changes`` -> (labels per model, the engine's table as nested tuples
+        [R][C][N] or None for the unit contrasts).  A dict ``label -> {series name: weight}`` is applied to every model that has
+        all of the label's series; the models with fewer labels are padded with all-zero contrasts."""
+        if contrasts is None:
+            return [list(self.batch.names[r]) for r in range(self.R)], None
+        if not isinstance(contrasts, dict) or not contrasts:
+            raise ValueError("contrasts must be None or a non-empty dict label -> {series name: weight}")
+        labels, rows = [], []
+        for r in range(self.R):
+            names = list(self.batch.names[r])
+            mine, table = [], []
+            for label, weights in contrasts.items():
+                if not weights or not all(name in names for name in weights):
+                    continue
+                row = [0.0] * self.N
+                for name, weight in weights.items():
+                    row[names.index(name)] += float(weight)
+                mine.append(label)
+                table.append(tuple(row))
+            labels.append(mine)
+            rows.append(table)
+        C = max(len(t) for t in rows)
+        if C < 1:
+            raise KeyError("no model has the series of any contrast")
+        return labels, tuple(tuple(t + [(0.0,) * self.N] * (C - len(t))) for t in rows)
+
+    def get_window_means(self, windows, contrasts=None, alpha=None, standardized=False):
+        """The EXACT posterior mean and standard deviation of the mean of the smoothed signal over time windows
+        (``BatchedKalman.functionals``): one smoothing pass and the smoother's covariance across time, where
+        ``get_window_statistics`` needs an ensemble of draws for an sd that is right to 1/sqrt(2 ndraws).  ``windows`` as in
+        ``get_window_statistics`` (``metran_amd.windows.step_windows``), except that explicit ``(start, stop)`` pairs may overlap
+        and come in any order.  ``contrasts``: None = every series, or a dict ``label -> {series name: weight}`` -- the head
+        difference of two wells ``{"gradient": {"w1": 1, "w2": -1}}``, the mean of a group -- applied to every model that has
+        those series.  It is the signal ``Z x`` whose mean is taken, as in ``get_simulated_means``: no observation variance is
+        added.  Returns a DataFrame: rows (model, series or label, window start), columns ``mean`` and ``sd`` in original units
+        (``standardized=True``: the units the filter runs in); a window without a step of the model is NaN."""
+        from pandas import DataFrame
+
+        from .windows import step_windows
+
+        steps, starts = step_windows(self.batch.index, windows, self.T, overlap=True)
+        labels, table = self._contrast_table(contrasts)
+        request = (tuple(tuple((int(a), int(b), 0, 0) for a, b in model) for model in steps), table, bool(standardized))
+        out = self._run("functionals", alpha, request)
+        mean, sd = out["mean"].cpu().numpy(), np.sqrt(out["var"].cpu().numpy())      # [R,W,C]
+        values = [np.stack([mean[r, : len(starts[r]), : len(labels[r])].T.reshape(-1), sd[r, : len(starts[r]), : len(labels[r])].T.reshape(-1)],
+                           axis=1) for r in range(self.R)]
+        return DataFrame(np.concatenate(values, axis=0),
+                         index=self._rows(lambda r: ((label, start) for label in labels[r] for start in starts[r]), ["series", "window"]),
+                         columns=["mean", "sd"])
+
+    def get_window_mean(self, r, name, windows, alpha=None, standardized=False):
+        """The rows of ``get_window_means`` for series ``name`` of model ``r``: DataFrame indexed by window start."""
+        self._series(r, name)
+        return self.get_window_means(windows, None, alpha, standardized).loc[(r + self.shard[0], name)]
+
+    def get_changes(self, period_a, period_b, contrasts=None, alpha=None, standardized=False):
+        """The change between two periods with its exact standard error: per model and series (or contrast label) the mean of the
+        smoothed signal over ``period_a`` minus its mean over ``period_b`` -- each a ``(start, stop)`` pair of timestamps, half
+        open, disjoint, in either order -- with the covariance between the two periods' steps taken from the smoother's
+        covariance across time.  Returns a DataFrame with one row per (model, series or label): ``estimate``, ``sd``, ``z`` =
+        estimate / sd and the two-sided normal ``pvalue``; NaN for a model without a step in one of the periods."""
+        from pandas import DataFrame
+        from scipy.stats import norm
+
+        from .windows import step_windows
+
+        sa, _ = step_windows(self.batch.index, [tuple(period_a)], self.T, overlap=True)
+        sb, _ = step_windows(self.batch.index, [tuple(period_b)], self.T, overlap=True)
+        rows = []
+        for (a0, a1), (b0, b1) in zip(sa[:, 0], sb[:, 0]):
+            if a0 < a1 and b0 < b1 and max(a0, b0) < min(a1, b1):
+                raise ValueError("period_a and period_b must not overlap")
+            rows.append(((int(a0), int(a1), int(b0), int(b1)) if b0 < b1 else (self.T, self.T, 0, 0),))   # a period without a step: NaN
+        labels, table = self._contrast_table(contrasts)
+        out = self._run("functionals", alpha, (tuple(rows), table, bool(standardized)))
+        est, var = out["mean"].cpu().numpy()[:, 0], out["var"].cpu().numpy()[:, 0]   # [R,C]
+        est = np.concatenate([est[r, : len(labels[r])] for r in range(self.R)])
+        sd = np.sqrt(np.concatenate([var[r, : len(labels[r])] for r in range(self.R)]))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            z = est / sd
+        return DataFrame({"estimate": est, "sd": sd, "z": z, "pvalue": 2.0 * norm.sf(np.abs(z))},
+                         index=self._rows(lambda r: ((label,) for label in labels[r]), ["series"]))
 
     # ------------------------------------------------------------------ one series' simulation and its decomposition
     def get_simulation(self, r, name, alpha=None, ci=0.05, standardized=False, method="smoother"):

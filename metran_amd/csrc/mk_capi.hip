@@ -15,6 +15,7 @@
 #include "draw_kernels.h"
 #include "ensemble_kernels.h"
 #include "forecast_kernels.h"
+#include "functional_kernels.h"
 #include "innov_kernels.h"
 #include "mk_generic.h"
 #include "mk_internal.h"
@@ -1807,6 +1808,87 @@ MK_API int mk_regression_adjust(mk_context *ctx, int64_t R, int64_t T, int64_t N
     a.in = d_obs_in;
     a.out = d_obs_out;
     MK_HIP(mk::launch_regress_adjust(a, ctx->stream));
+    return MK_OK;
+}
+
+// ---- exact window means, changes and contrasts of the smoothed signal (functional_kernels.hip) ----
+MK_API int64_t mk_functionals_max_contrasts(void) { return mk::functional_max_contrasts; }
+
+MK_API int64_t mk_functionals_work_stride(int64_t N, int64_t K)
+{
+    if (N < 1 || K < 1 || N + K > mk::functional_max_states || !mk_shape_supported(N, K)) return 0;
+    return 2 * (int64_t)mk::record_stride((int)(N + K)); // the filtered and the smoothed record of a step
+}
+
+MK_API int mk_functionals(mk_context *ctx, const mk_problem *p, double *d_work, int time_major, const mk_functional_request *req,
+                          double *d_mean, double *d_var, uint32_t *d_status)
+{
+    MK_CTX(ctx);
+    // refused first: every other shape that mk_functionals_work_stride does not serve is one check_problem refuses
+    if (p && p->N >= 1 && p->K >= 1 && p->N + p->K > mk::functional_max_states)
+        return too_many_states("mk_functionals", p, mk::functional_max_states);
+    if (int rc = check_problem(p)) return rc;
+    if (!req) return fail(MK_ERR_INVALID, "mk_functionals: null mk_functional_request");
+    if (!d_work) return fail(MK_ERR_INVALID, "mk_functionals: d_work is required");
+    if (!req->d_windows || !d_mean || !d_var) return fail(MK_ERR_INVALID, "mk_functionals: d_windows, d_mean and d_var are required");
+    if (req->n_windows < 1) return fail(MK_ERR_INVALID, "mk_functionals: need n_windows >= 1 (got %lld)", (long long)req->n_windows);
+    if (req->n_contrasts < 1 || req->n_contrasts > mk::functional_max_contrasts)
+        return fail(MK_ERR_INVALID, "mk_functionals: need 1 <= n_contrasts <= %d (got %lld)", mk::functional_max_contrasts,
+                    (long long)req->n_contrasts);
+    if (!req->d_contrasts && req->n_contrasts != p->N)
+        return fail(MK_ERR_INVALID, "mk_functionals: d_contrasts = NULL stands for the N unit contrasts, n_contrasts must be N = %lld (got %lld)",
+                    (long long)p->N, (long long)req->n_contrasts);
+    if (!p->d_obs || !p->d_loadings) return fail(MK_ERR_INVALID, "d_obs and d_loadings are required");
+    const int64_t ws = mk_functionals_work_stride(p->N, p->K);
+    if (!ws) return too_many_states("mk_functionals", p, mk::functional_max_states);
+    const int64_t B = p->n_instances, W = req->n_windows, C = req->n_contrasts, n = p->N + p->K;
+    const int64_t rs = mk::record_stride((int)n);
+    static_assert(sizeof(int64_t) == sizeof(double), "buffers_fit counts 8-byte words");
+    const device_buffer bufs[5] = {{d_work, B * p->T * ws, "d_work (n_instances * T * mk_functionals_work_stride(N, K) doubles)"},
+                                   {req->d_windows, p->n_records * W * 4, "d_windows (n_records * n_windows * 4 64-bit integers)"},
+                                   {req->d_contrasts, p->n_records * C * p->N, "d_contrasts (n_records * n_contrasts * N doubles)"},
+                                   {d_mean, B * W * C, "d_mean (n_instances * n_windows * n_contrasts doubles)"},
+                                   {d_var, B * W * C, "d_var (n_instances * n_windows * n_contrasts doubles)"}};
+    if (int rc = buffers_fit("mk_functionals", bufs, 5)) return rc;
+    // the filtered records are packed at the head of d_work, the smoothed ones behind them: the forward pass and the smoother of
+    // mk_filter_smooth for the shape (full-square records, no projection), then the walk
+    if (int rc = record_pass(ctx, p, d_work, rs, time_major, d_status)) return rc;
+    double *smoothed = d_work + B * p->T * rs;
+    mk_outputs o;
+    memset(&o, 0, sizeof(o));
+    o.d_status = d_status;
+    o.d_F = d_work;
+    o.d_Pf = d_work + n;
+    o.d_S = smoothed;
+    o.d_Ps = smoothed + n;
+    o.time_major = time_major;
+    o.record_stride = rs;
+    if (int rc = do_smooth(ctx, p, &o, false)) return rc;
+    mk::FunctionalArgs a;
+    memset(&a, 0, sizeof(a));
+    a.B = B;
+    a.R = p->n_records;
+    a.T = p->T;
+    a.W = W;
+    a.C = C;
+    a.N = (int)p->N;
+    a.K = (int)p->K;
+    fill_layout(a, time_major, B, p->T);
+    fill_scaling(a, p);
+    a.rs = rs;
+    a.phi = p->d_phi;
+    a.q = p->d_q;
+    a.loadings = p->d_loadings;
+    a.F = d_work;
+    a.S = smoothed;
+    a.windows = req->d_windows;
+    a.contrasts = req->d_contrasts;
+    a.mean = d_mean;
+    a.var = d_var;
+    a.status = d_status;
+    MK_HIP(timing_start(ctx, 1));
+    MK_HIP(mk::launch_functional_walk(a, ctx->stream));
+    MK_HIP(timing_stop(ctx, 1)); // reported in the smoother slot of mk_last_kernel_ms / mk_kernel_ms_totals, beside the smoother's own launch
     return MK_OK;
 }
 

@@ -14,7 +14,7 @@ import logging
 import numpy as np
 
 from . import _lib
-from ._lib import ForecastRequest, MetranHipError, Outputs, Problem, RegressionRequest, WeightsRequest, check
+from ._lib import ForecastRequest, FunctionalRequest, MetranHipError, Outputs, Problem, RegressionRequest, WeightsRequest, check
 
 logger = logging.getLogger(__name__)
 
@@ -709,9 +709,9 @@ class BatchedKalman:
         return res
 
     # ------------------------------------------------------------------ the record readers: one scaffold
-    # loo_predict, disturbances, innovations, forecast, observation_weights and regression run the recording forward pass into a workspace ("_work") and one kernel
+    # loo_predict, disturbances, innovations, forecast, observation_weights, regression and functionals (which also runs the smoother) run the recording forward pass into a workspace ("_work") and one kernel
     # that reads its filtered records.  NOTE: loo_supported() and disturbances_supported() are methods, innovations_supported and
-    # forecast_supported / observation_weights_supported / regression_supported properties -- an inconsistency of the public API that is kept.
+    # forecast_supported / observation_weights_supported / regression_supported / functionals_supported properties -- an inconsistency of the public API that is kept.
     def _reader_stride(self, fn, specialised_only, refusal=None):
         """Doubles per (instance, step) of a record reader's workspace, the C ABI's ``fn(N, K)``; where the shape is not served
         0, or with ``refusal`` (a text with places for N and K) a MetranHipError."""
@@ -1110,6 +1110,78 @@ class BatchedKalman:
         check(self._L.mk_regression(self._ctx, ctypes.byref(prob), self._p(res["_work"]), 1 if self.time_major else 0,
                                     ctypes.byref(req), self._p(res["status"])))
         self._mask_bad_instances(res, ("beta", "cov", "gain", "normal"))
+        return res
+
+    # ------------------------------------------------------------------ exact window means, changes and contrasts
+    @property
+    def functionals_supported(self):
+        """True when ``functionals`` serves this engine (C ABI ``mk_functionals_work_stride`` > 0): N + K <= 64, specialised or
+        size-generic kernels alike, full-square records."""
+        return not self.packed_sym and self._reader_stride(self._L.mk_functionals_work_stride, False) > 0
+
+    def _functionals_stride(self):
+        if self.packed_sym:
+            raise MetranHipError("libmetran_hip error -2 (MK_ERR_SHAPE): window functionals read full-square records; this engine was "
+                                 "created with packed_sym=True")
+        return self._reader_stride(self._L.mk_functionals_work_stride, False,
+                                   "window functionals serve shapes with N + K <= 64; (N=%s, K=%s) is not one")
+
+    def _functionals_shapes(self, B, W, C):
+        """name -> (logical shape, follows the engine's layout) of the buffers of ``functionals``."""
+        shapes = self._bt_shapes(B, _work=self._functionals_stride())
+        shapes.update(mean=((B, W, C), False), var=((B, W, C), False))
+        return shapes
+
+    def _functionals_counts(self, W, C):
+        W, C, cmax = int(W), int(C), int(self._L.mk_functionals_max_contrasts())
+        if W < 1 or not 1 <= C <= cmax:
+            raise ValueError("need W >= 1 windows and 1 <= C <= %d contrasts (got W = %d, C = %d)" % (cmax, W, C))
+        return W, C
+
+    def alloc_functionals(self, B, W, C):
+        """Buffers of ``functionals`` for B instances, W windows and C contrasts per record (the workspace of the filtered and the
+        smoothed records + the two outputs), for callers that run it repeatedly (pass them back as ``buffers=``)."""
+        W, C = self._functionals_counts(W, C)
+        return self._reader_buffers(None, self._functionals_shapes(B, W, C), "alloc_functionals", sep=", ")
+
+    def functionals(self, phi, q, windows, contrasts=None, x0=None, P0=None, buffers=None):
+        """EXACT posterior mean and variance of linear functionals of the smoothed signal for B instances (C ABI
+        ``mk_functionals``): ``l = sum_t alpha_t c'(scale o Z x_t + offset)`` with ``alpha_t = 1/(t1 - t0)`` on ``[t0, t1)`` and
+        ``-1/(t3 - t2)`` on ``[t2, t3)`` -- the mean over a window (``t2 == t3``), a point value (``t1 - t0 == 1``) or the
+        difference of two periods' means -- from the smoother's covariance across time (the smoothed state autocovariance), never
+        from draws.  ``windows``: ``[R,W,4]`` integers ``(t0, t1, t2, t3)`` (or ``[W,4]``, shared by the records), clamped to
+        ``[0, T]``; ``contrasts``: ``[R,C,N]`` weights of the series (or ``[C,N]``, shared), None = the N unit contrasts; instance
+        b uses the windows and contrasts of record ``b % R``.  Units as set by ``set_scaling``; no observation variance is added.
+        Returns a dict with ``mean, var [B,W,C]`` and ``status`` (the filter's and the smoothers' MK_FLAG_* bits); a functional whose
+        first range is empty is NaN; the rows of an instance whose status carries ``FLAG_NONPOSITIVE_F`` are NaN.  Three launches
+        (the recording forward pass, the smoother, one walk per window); an instance's results do not depend on the batch, on the
+        other windows or on the other contrasts, bit for bit."""
+        torch = _torch()
+        self._functionals_stride()
+        wn = torch.as_tensor(windows, dtype=torch.int64)
+        if wn.ndim == 2:
+            wn = wn[None].expand(self.R, -1, -1)
+        if wn.ndim != 3 or wn.shape[0] != self.R or wn.shape[1] < 1 or wn.shape[2] != 4:
+            raise ValueError("windows must be [%d,W,4] (or [W,4]) integers (t0, t1, t2, t3), W >= 1" % self.R)
+        wn = wn.to(self.device).contiguous()
+        ct = None
+        if contrasts is not None:
+            ct = torch.as_tensor(contrasts, dtype=torch.float64)
+            if ct.ndim == 2:
+                ct = ct[None].expand(self.R, -1, -1)
+            if ct.ndim != 3 or ct.shape[0] != self.R or ct.shape[2] != self.N:
+                raise ValueError("contrasts must be [%d,C,%d] (or [C,%d]) weights of the series" % (self.R, self.N, self.N))
+            ct = ct.to(self.device).contiguous()
+        W, C = self._functionals_counts(wn.shape[1], self.N if ct is None else ct.shape[1])
+        prob, keep, B = self._problem(phi, q, 0, x0, P0)
+        res = self._reader_buffers(buffers, self._functionals_shapes(B, W, C), "alloc_functionals", sep=", ")
+        req = FunctionalRequest()
+        req.n_windows, req.n_contrasts = W, C
+        req.d_windows, req.d_contrasts = wn.data_ptr(), None if ct is None else ct.data_ptr()
+        self._bind_stream()
+        check(self._L.mk_functionals(self._ctx, ctypes.byref(prob), self._p(res["_work"]), 1 if self.time_major else 0,
+                                     ctypes.byref(req), self._p(res["mean"]), self._p(res["var"]), self._p(res["status"])))
+        self._mask_bad_instances(res, ("mean", "var"))
         return res
 
     def adjust_observations(self, effects, beta):

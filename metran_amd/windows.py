@@ -1,4 +1,4 @@
-"""Time windows of ``MetranBatch.get_window_statistics``, translated to step ranges: a pure host function (pandas and numpy, no
+"""Time windows of ``MetranBatch.get_window_statistics`` and ``get_window_means``, translated to step ranges: a pure host function (pandas and numpy, no
 engine).  Step ``t`` of model ``r`` is in the window ``(start, stop)`` when ``start <= index[r][t] < stop``; a model's steps are
 those of its own index, so the padded steps beyond its length are in no window."""
 import numpy as np
@@ -20,10 +20,11 @@ def _edges(index, alias):
     return DatetimeIndex(edges)
 
 
-def step_windows(indexes, windows, T):
+def step_windows(indexes, windows, T, overlap=False):
     """``indexes``: one increasing ``DatetimeIndex`` per model (its length at most ``T``); ``windows``: a pandas offset alias
     (``"MS"``, ``"YS"``, ``"W"``, ...: the windows between consecutive ticks of the offset that cover the model's index) or a
-    list of ``(start, stop)`` timestamps, sorted and not overlapping.  Returns ``(steps, starts)``: ``steps`` int64 ``[R,W,2]``
+    list of ``(start, stop)`` timestamps, sorted and not overlapping (``overlap=True``: in any order, overlapping or not -- the
+    exact window means are computed window by window).  Returns ``(steps, starts)``: ``steps`` int64 ``[R,W,2]``
     half-open step ranges ``[a, b)`` per model -- a window without a step of the model is empty (``a == b``), models with fewer
     windows are padded with ``(T, T)`` -- and ``starts``, per model the ``DatetimeIndex`` of its windows' starts."""
     from pandas import DatetimeIndex, Timestamp
@@ -44,7 +45,9 @@ def step_windows(indexes, windows, T):
             if not pairs:
                 raise ValueError("windows is empty")
             start, stop = DatetimeIndex([p[0] for p in pairs]), DatetimeIndex([p[1] for p in pairs])
-            if (stop < start).any() or (start[1:] < stop[:-1]).any():
+            if overlap and (stop < start).any():
+                raise ValueError("every window needs start <= stop")
+            if not overlap and ((stop < start).any() or (start[1:] < stop[:-1]).any()):
                 raise ValueError("windows must be sorted and must not overlap: start <= stop <= the next window's start")
         spans.append((start, np.stack([index.searchsorted(start, side="left"), index.searchsorted(stop, side="left")], axis=1)))
     W = max(len(s[0]) for s in spans)
