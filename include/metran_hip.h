@@ -656,6 +656,48 @@ MK_API int mk_regression(mk_context *ctx, const mk_problem *prob, double *d_work
 MK_API int mk_regression_adjust(mk_context *ctx, int64_t R, int64_t T, int64_t N, int time_major, int64_t n_effects,
                                 const int64_t *d_effects, const double *d_beta, const double *d_obs_in, double *d_obs_out);
 
+/* ---- per-step scores by the tangent filter (score_kernels.hip) ------------------------------------------------------------------
+ * The SCORE of every time step: the derivative of the step's contribution to -2 log L, l_t = sum_j (log f_{t,j} + v_{t,j}^2 /
+ * f_{t,j}) over the cells observed at t (the constant of get_mle is not differentiated), with respect to one parameter per state
+ * (what statsmodels calls score_obs), and the sums built on them.  Model and filter order as in mk_innovations; d_{t,j} and
+ * rf_{t,j} = 1 / f_{t,j} of every scalar update as in mk_observation_weights (zero at a cell that is not observed).
+ *   Parameter p (0 <= p < n = N + K) moves phi_p and q_p only: d_dphi[b,p] = d phi_p / d theta_p and d_dq[b,p] = d q_p / d theta_p
+ * are inputs, the chain rule to the caller's parameters stays outside.  x0 and P0 do not depend on the parameters.  The tangent
+ * (Pd symmetric n x n, xd) of pair (b, p) starts at zero; with x, P the FILTERED moments of step t - 1 (x0, P0 at t = 0):
+ *     predict   xd <- phi o xd + dphi x_p e_p;   Pd <- Phi Pd Phi + dphi (e_p (P_p. o phi) + (phi o P_.p) e_p') + dq e_p e_p'
+ *     cell j    dd = Pd z_j',  fd = z_j dd,  vd = -z_j xd;      s_{t,p} += fd rf + 2 v vd rf - v^2 fd rf^2
+ *               xd <- xd + (dd v + d vd) rf - d v fd rf^2;      Pd <- Pd - (dd d' + d dd') rf + d d' fd rf^2
+ * A step is COUNTED when t >= t_first and it holds at least one observation; m = d_count[b] (int64) is their number.
+ *   d_score [B,T,n] (stored [T,B,n] when time_major is set)   s_{t,p} of every step, zero at an empty step, also for t < t_first
+ *   d_grad  [B,n]     sum of s_t over the counted steps
+ *   d_opg   [B,n,n]   sum of s_t s_t' over the counted steps: positive semi-definite by construction
+ *   d_cusum [B,n,n]   sum of S_t S_t' over the counted steps, S_t = sum_{u <= t, counted} (s_u - grad / m): the tied-down cumulative
+ *                     scores of the Nyblom-Hansen test of parameter constancy
+ *   Launches: as mk_observation_weights -- the recording forward pass into d_work (n_instances * T * mk_scores_work_stride(N, K)
+ * doubles = the weights stride + N: records, then the gain tape, then one row of N innovations per (instance, step)), the clear
+ * of the tape, innov_step_kernel writing the tape and v -- then score_tangent_kernel (one lane group per (instance, parameter),
+ * lane = state) and score_stats_kernel (one workgroup per instance), timed in the smoother slot of mk_last_kernel_ms /
+ * mk_kernel_ms_totals.  Every sum has a fixed order: an instance's outputs are bit-identical whatever the batch, the layout of
+ * d_work or the neighbouring instances.  prob->warmup is ignored (t_first says which steps count); d_status (may be NULL) receives
+ * the filter's MK_FLAG_* bits -- the outputs of an instance with MK_FLAG_NONPOSITIVE_F are not meaningful.
+ *   Served: every supported shape with N + K <= mk_scores_max_states() = 64, under either kernel family, full-square records;
+ * mk_scores_work_stride returns 0 otherwise and mk_scores fails with MK_ERR_SHAPE.  MK_ERR_INVALID (no launch): a missing pointer
+ * (all of the request's are required), t_first < 0, a buffer larger than the allocation it points into. */
+typedef struct mk_scores_request {
+    const double *d_dphi;         /* [B, n] */
+    const double *d_dq;           /* [B, n] */
+    int64_t t_first;              /* the steps t >= t_first that hold an observation are counted (1: as Metran's warm-up) */
+    double *d_score;              /* [B, T, n] */
+    double *d_grad;               /* [B, n] */
+    int64_t *d_count;             /* [B] */
+    double *d_opg;                /* [B, n, n] */
+    double *d_cusum;              /* [B, n, n] */
+} mk_scores_request;
+MK_API int64_t mk_scores_max_states(void);
+MK_API int64_t mk_scores_work_stride(int64_t N, int64_t K);
+MK_API int mk_scores(mk_context *ctx, const mk_problem *prob, double *d_work, int time_major, const mk_scores_request *req,
+                     uint32_t *d_status);
+
 /* ---- exact window means, changes and contrasts of the smoothed signal (functional_kernels.hip) --------------------------------
  * The posterior mean and variance of LINEAR functionals of the smoothed path, per instance b (record r = b % n_records), window w
  * and contrast c:

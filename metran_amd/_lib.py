@@ -8,7 +8,7 @@ import ctypes
 import os
 from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
 
-__all__ = ["MetranHipError", "lib", "library_path", "Problem", "Outputs", "ForecastRequest", "WeightsRequest", "RegressionRequest", "check", "API"]
+__all__ = ["MetranHipError", "lib", "library_path", "Problem", "Outputs", "ForecastRequest", "WeightsRequest", "RegressionRequest", "ScoresRequest", "check", "API"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIBNAME = "libmetran_hip.so"
@@ -115,6 +115,21 @@ class RegressionRequest(Structure):
     ]
 
 
+class ScoresRequest(Structure):
+    """``mk_scores_request`` (include/metran_hip.h)."""
+
+    _fields_ = [
+        ("d_dphi", c_void_p),
+        ("d_dq", c_void_p),
+        ("t_first", c_int64),
+        ("d_score", c_void_p),
+        ("d_grad", c_void_p),
+        ("d_count", c_void_p),
+        ("d_opg", c_void_p),
+        ("d_cusum", c_void_p),
+    ]
+
+
 class FunctionalRequest(Structure):
     """``mk_functional_request`` (include/metran_hip.h)."""
 
@@ -201,6 +216,9 @@ API = {
     "mk_regression_work_stride": (c_int64, [c_int64, c_int64]),
     "mk_regression": (c_int, [c_void_p, POINTER(Problem), c_void_p, c_int, POINTER(RegressionRequest), c_void_p]),
     "mk_regression_adjust": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mk_scores_max_states": (c_int64, []),
+    "mk_scores_work_stride": (c_int64, [c_int64, c_int64]),
+    "mk_scores": (c_int, [c_void_p, POINTER(Problem), c_void_p, c_int, POINTER(ScoresRequest), c_void_p]),
     "mk_functionals_max_contrasts": (c_int64, []),
     "mk_functionals_work_stride": (c_int64, [c_int64, c_int64]),
     "mk_functionals": (c_int, [c_void_p, POINTER(Problem), c_void_p, c_int, POINTER(FunctionalRequest), c_void_p, c_void_p, c_void_p]),

@@ -17,6 +17,9 @@ number comes from the HIP kernels:
                                  get_weight_shares)
     regression               ->  intervention effects by GLS: level shifts, outliers and trends of single series
                                  (fit_interventions, adjust_observations)
+    scores_alpha             ->  per-step scores of the parameters by the tangent filter: OPG and robust standard errors,
+                                 the Nyblom-Hansen test of parameter constancy (get_scores, get_parameter_covariance,
+                                 test_parameter_stability)
     functionals              ->  exact window means, changes between periods and contrasts of series, from the smoother's
                                  covariance across time (get_window_means, get_window_mean, get_changes)
     draw_smoothed            ->  posterior draws of series and states (get_simulation_draws, get_state_draws)
@@ -27,7 +30,7 @@ table (``_KINDS``): ``_cache[kind] = (parameter set, {request: kept result})``. 
 parameter set -- different kinds may hold different ones -- and of that result only the keys its accessors read (the table's
 keep-list: never the forward pass's workspace, the records or the tape, which are hundreds of times the outputs), plus what
 the accessors derive from them once (``("simf", standardized)``, ``("decomp", standardized)``).  The kinds with a request
-(``forecast``, ``weights``, ``regress``, ``functionals``) keep every request of their parameter set; another parameter set drops them all.  ``solve``,
+(``forecast``, ``weights``, ``regress``, ``functionals``, ``scores``, ``hessian``) keep every request of their parameter set; another parameter set drops them all.  ``solve``,
 ``mask_observations``, ``unmask_observations``, ``adjust_observations`` and ``unadjust_observations`` clear the cache.  So asking for another series, the variances after the
 means, or the decomposition after the simulation does not launch anything.  The draws and their window statistics are not
 cached: an ensemble is the size of the thing it summarises.
@@ -82,6 +85,32 @@ def _functionals(mb, phi, q, request):
         mb.kf.set_scaling(mb._std, mb._mean)
 
 
+def _scores(mb, alpha, request):
+    """request = t_first.  The derivatives are Metran's, with respect to alpha: the engine forms them from the parameter set itself."""
+    return mb.kf.scores_alpha(alpha, dt=mb.dt, t_first=request)
+
+
+def _hessian(mb, alpha, request):
+    """request = t_first: the Hessian of -2 log L with respect to alpha, differenced from the adjoint gradient as
+    ``calibrate_batch(stderr=True)`` does, over the steps the scores count.  The filter's warm-up skips steps that HOLD an
+    observation, so a record's warm-up is the number of its non-empty steps before t_first; the records are taken in groups
+    of equal warm-up (one group, the whole engine, unless records begin with empty steps)."""
+    import torch
+
+    from .scores import hessian_alpha
+
+    kf = mb.kf
+    warm = torch.isfinite(kf.obs[:, :request]).any(2).sum(1).cpu().numpy() if request > 0 else np.zeros(mb.R, dtype=np.int64)
+    hess = torch.empty((mb.R, mb.N + mb.K, mb.N + mb.K), dtype=torch.float64, device=alpha.device)
+    for w in np.unique(warm):
+        idx = np.nonzero(warm == w)[0]
+        whole = idx.size == mb.R
+        part = hessian_alpha(kf if whole else kf.subset(idx), alpha if whole else alpha[torch.as_tensor(idx, device=alpha.device)],
+                             dt=mb.dt, warmup=int(w))
+        hess[torch.as_tensor(idx, device=hess.device)] = part
+    return {"hessian": hess, "status": torch.zeros(mb.R, dtype=torch.int32, device=hess.device)}
+
+
 # kind -> (engine call (facade, phi, q, request), whether the scaling is set first, keys of the result that are kept).
 # The scaling is set where the call writes ORIGINAL units: the projection, the leave-one-out predictions, the one- and
 # multi-step-ahead forecasts.  "q" is the q the run was computed for.
@@ -105,6 +134,13 @@ _FIT_KINDS = {
     "regress": (_regress, False, ("beta", "cov", "gain", "normal", "support", "dropped", "obj")),
     # exact moments of linear functionals of the smoothed signal, in the units the request names
     "functionals": (_functionals, False, ("mean", "var")),
+}
+# The kinds whose engine call takes the parameter set itself, alpha, not (phi, q): kind -> (engine call (facade, alpha, request),
+# keys of the result that are kept).  The same cache and the same status check, through ``MetranBatch._run``.
+_ALPHA_KINDS = {
+    # per-step scores with respect to alpha and their sums; the Hessian that the "hessian" and "robust" covariances need
+    "scores": (_scores, ("score", "grad", "count", "opg", "cusum")),
+    "hessian": (_hessian, ("hessian",)),
 }
 
 
@@ -250,19 +286,25 @@ class MetranBatch:
 
     # ------------------------------------------------------------------ cached kernel runs (Metran._run_kalman)
     def _run(self, kind, alpha, request=None):
-        """The result of ``_KINDS[kind]`` (or ``_FIT_KINDS[kind]``) for the parameter set and the (hashable) ``request``: from the cache, or from the engine
+        """The result of ``_KINDS[kind]`` (or ``_FIT_KINDS[kind]``, ``_ALPHA_KINDS[kind]``) for the parameter set and the (hashable) ``request``: from the cache, or from the engine
         and then kept -- the keys of the kind's keep-list, nothing else.  A kind holds the results of one parameter set
         (metran.py:978-989 keeps one too); another parameter set replaces them once its own run has passed the status check."""
         import torch
 
-        call, scaling, keep = _KINDS[kind] if kind in _KINDS else _FIT_KINDS[kind]
         a = self._alpha(alpha)
         hit = self._cache.get(kind)
         if hit is None or hit[0].shape != a.shape or not bool(torch.equal(hit[0], a)):
             hit = (a.clone(), {})
         if request not in hit[1]:
-            out, q = self._launch(kind, a, scaling, lambda phi, q: call(self, phi, q, request))
-            hit[1][request] = {key: value for key, value in dict(out, q=q).items() if key in keep}
+            if kind in _ALPHA_KINDS:
+                call, keep = _ALPHA_KINDS[kind]
+                out = call(self, a, request)
+                check_status(out["status"].reshape(-1), "MetranBatch(%s)" % kind)
+            else:
+                call, scaling, keep = _KINDS[kind] if kind in _KINDS else _FIT_KINDS[kind]
+                out, q = self._launch(kind, a, scaling, lambda phi, q: call(self, phi, q, request))
+                out = dict(out, q=q)
+            hit[1][request] = {key: value for key, value in out.items() if key in keep}
             self._cache[kind] = hit
         return hit[1][request]
 
@@ -695,6 +737,71 @@ class MetranBatch:
         """The records as they were before ``adjust_observations``."""
         self.kf.unadjust_observations()
         self._cache.clear()
+
+    # ------------------------------------------------------------------ scores of the parameters (uncertainty, stability)
+    def _parameter_names(self, r):
+        return [c + "_alpha" for c in self._state_columns(r)]
+
+    def _parameter_exists(self):
+        """``[R,N+K]`` bool: False for the surplus factor parameters of a model with fewer factors than the batch maximum."""
+        return np.arange(self.N + self.K)[None, :] < (self.N + np.asarray(self.nfactors))[:, None]
+
+    def get_scores(self, r, alpha=None, t_first=1):
+        """The per-step scores of model ``r`` (``BatchedKalman.scores_alpha``; what statsmodels calls ``score_obs``): DataFrame on
+        the model's index, one column per parameter (``<series>_sdf_alpha`` ..., ``cdf1_alpha`` ...), the derivative of every
+        step's contribution to -2 log L with respect to that alpha; 0 at a step without observations.  Every step is there,
+        also those before ``t_first`` (which only says what the sums count: it is part of the cache key)."""
+        from pandas import DataFrame
+
+        out = self._run("scores", alpha, int(t_first))
+        L = int(self.batch.lengths[r])
+        return DataFrame(out["score"][r, :L].cpu().numpy(), index=self.batch.index[r], columns=self._parameter_names(r))
+
+    def get_parameter_covariance(self, kind="robust", alpha=None, t_first=1):
+        """Covariance of the parameter estimates of every model (``metran_amd.scores.parameter_covariance``): ``"opg"`` =
+        4 pinv(sum s s') from the per-step scores, positive semi-definite by construction and available for every shape the
+        scores serve; ``"hessian"`` = 2 pinv(H) and ``"robust"`` = pinv(H) opg pinv(H) (the sandwich: trustworthy when the model is
+        slightly wrong), H the Hessian of -2 log L differenced from the adjoint gradient exactly as ``solve(stderr=True)`` does
+        -- where the shape has no adjoint gradient those two raise its message.  ``fit["pcov"]`` keeps the reference's pinv(H),
+        half of ``"hessian"``.  The steps ``t >= t_first`` that hold an observation count, in the scores and in the Hessian alike
+        (its warm-up is each record's number of non-empty steps before ``t_first``).  Returns a dict of numpy arrays ``pcov
+        [R,n,n]``, ``stderr [R,n]`` and ``corr [R,n,n]``; NaN for the parameters a model does not have."""
+        from .scores import COVARIANCE_KINDS, parameter_covariance
+
+        if kind not in COVARIANCE_KINDS:
+            raise ValueError("kind must be one of %s" % ", ".join(repr(k) for k in COVARIANCE_KINDS))
+        hess = None if kind == "opg" else self._run("hessian", alpha, int(t_first))["hessian"]
+        out = self._run("scores", alpha, int(t_first))
+        pcov = parameter_covariance(out["opg"], out["count"], out["grad"], hess, kind).cpu().numpy()
+        gone = ~self._parameter_exists()
+        pcov = np.where(gone[:, :, None] | gone[:, None, :], np.nan, pcov)
+        var = np.diagonal(pcov, axis1=1, axis2=2)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            se = np.sqrt(np.where(var >= 0, var, np.nan))
+            corr = pcov / (se[:, :, None] * se[:, None, :])
+        return {"pcov": pcov, "stderr": se, "corr": corr}
+
+    def test_parameter_stability(self, alpha=None, t_first=1):
+        """Nyblom-Hansen test of parameter constancy (``metran_amd.scores.nyblom``): are the response times constant over the
+        record?  The parameter-side counterpart of ``screen_breaks``: a well field that started pumping half-way changes a
+        series' alpha without necessarily producing one large state disturbance.  DataFrame indexed (model, parameter) with
+        ``L`` (the statistic), ``pvalue`` (``cvm_sf(L, 1)``; small = the parameter moved) and ``n_steps`` (the counted steps: ``t
+        >= t_first`` with an observation), and per model a row ``joint`` over all its parameters (``cvm_sf(L, k)``).  The scores are
+        centred, so the test is also meaningful at a bound or for a model that has not converged.  NaN for the parameters a
+        model does not have."""
+        from pandas import DataFrame
+
+        from .scores import nyblom
+
+        out = self._run("scores", alpha, int(t_first))
+        count = out["count"].cpu().numpy()
+        res = nyblom(out["cusum"].cpu().numpy(), out["opg"].cpu().numpy(), out["grad"].cpu().numpy(), count, self._parameter_exists())
+        rows = {"L": [], "pvalue": [], "n_steps": []}
+        for r in range(self.R):
+            rows["L"] += list(res["L_param"][r]) + [res["L"][r]]
+            rows["pvalue"] += list(res["pvalue_param"][r]) + [res["pvalue"][r]]
+            rows["n_steps"] += [int(count[r])] * (self.N + self.K + 1)
+        return DataFrame(rows, index=self._rows(lambda r: [(name,) for name in self._parameter_names(r) + ["joint"]], ["parameter"]))
 
     # ------------------------------------------------------------------ state disturbances (break detection)
     def get_state_disturbances(self, alpha=None):

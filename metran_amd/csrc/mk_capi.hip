@@ -21,6 +21,7 @@
 #include "mk_internal.h"
 #include "mk_lbfgs.h"
 #include "regress_kernels.h"
+#include "score_kernels.h"
 #include "weights_kernels.h"
 
 struct mk_context {
@@ -1808,6 +1809,88 @@ MK_API int mk_regression_adjust(mk_context *ctx, int64_t R, int64_t T, int64_t N
     a.in = d_obs_in;
     a.out = d_obs_out;
     MK_HIP(mk::launch_regress_adjust(a, ctx->stream));
+    return MK_OK;
+}
+
+// ---- per-step scores by the tangent filter (score_kernels.hip) ----
+MK_API int64_t mk_scores_max_states(void) { return mk::score_max_states; }
+
+MK_API int64_t mk_scores_work_stride(int64_t N, int64_t K)
+{
+    static_assert(mk::score_max_states == mk::weights_max_states, "the scores run on the weights' workspace and a row of innovations");
+    const int64_t ws = mk_weights_work_stride(N, K);
+    return ws ? ws + N : 0;
+}
+
+MK_API int mk_scores(mk_context *ctx, const mk_problem *p, double *d_work, int time_major, const mk_scores_request *req, uint32_t *d_status)
+{
+    MK_CTX(ctx);
+    // refused first: every other shape that mk_scores_work_stride does not serve is one check_problem refuses
+    if (p && p->N >= 1 && p->K >= 1 && p->N + p->K > mk::score_max_states) return too_many_states("mk_scores", p, mk::score_max_states);
+    if (int rc = check_problem(p)) return rc;
+    if (!req) return fail(MK_ERR_INVALID, "mk_scores: null mk_scores_request");
+    if (!d_work) return fail(MK_ERR_INVALID, "mk_scores: d_work is required");
+    if (!req->d_dphi || !req->d_dq || !req->d_score || !req->d_grad || !req->d_count || !req->d_opg || !req->d_cusum)
+        return fail(MK_ERR_INVALID, "mk_scores: d_dphi, d_dq, d_score, d_grad, d_count, d_opg and d_cusum are required");
+    if (req->t_first < 0) return fail(MK_ERR_INVALID, "mk_scores: t_first must be >= 0");
+    if (!p->d_obs || !p->d_loadings) return fail(MK_ERR_INVALID, "d_obs and d_loadings are required");
+    const int64_t ws = mk_scores_work_stride(p->N, p->K);
+    if (!ws) return too_many_states("mk_scores", p, mk::score_max_states);
+    const int64_t B = p->n_instances, n = p->N + p->K;
+    const int64_t rs = mk::record_stride((int)n), gs = mk::weights_slot_stride(n);
+    static_assert(sizeof(int64_t) == sizeof(double), "buffers_fit counts 8-byte words");
+    const device_buffer bufs[8] = {{d_work, B * p->T * ws, "d_work (n_instances * T * mk_scores_work_stride(N, K) doubles)"},
+                                   {req->d_dphi, B * n, "d_dphi (n_instances * (N + K) doubles)"},
+                                   {req->d_dq, B * n, "d_dq (n_instances * (N + K) doubles)"},
+                                   {req->d_score, B * p->T * n, "d_score (n_instances * T * (N + K) doubles)"},
+                                   {req->d_grad, B * n, "d_grad (n_instances * (N + K) doubles)"},
+                                   {req->d_count, B, "d_count (n_instances 64-bit integers)"},
+                                   {req->d_opg, B * n * n, "d_opg (n_instances * (N + K)^2 doubles)"},
+                                   {req->d_cusum, B * n * n, "d_cusum (n_instances * (N + K)^2 doubles)"}};
+    if (int rc = buffers_fit("mk_scores", bufs, 8)) return rc;
+    // the records are packed at the head of d_work; the gain tape lives behind them, the innovations behind the tape
+    if (int rc = record_pass(ctx, p, d_work, rs, time_major, d_status)) return rc;
+    double *tape = d_work + B * p->T * rs;
+    double *innov = tape + B * p->T * p->N * gs;
+    mk::InnovArgs g;
+    memset(&g, 0, sizeof(g));
+    fill_model(g, p);
+    fill_initial(g, p);
+    fill_layout(g, time_major, B, p->T);
+    g.N = (int)p->N;
+    g.K = (int)p->K;
+    g.rs = rs;
+    g.F = d_work;
+    g.v = innov;
+    g.gain = tape;
+    g.gs = gs;
+    mk::ScoreArgs a;
+    memset(&a, 0, sizeof(a));
+    fill_model(a, p);
+    fill_initial(a, p);
+    fill_layout(a, time_major, B, p->T);
+    a.N = (int)p->N;
+    a.K = (int)p->K;
+    a.t_first = req->t_first;
+    a.rs = rs;
+    a.gs = gs;
+    a.F = d_work;
+    a.gain = tape;
+    a.v = innov;
+    a.dphi = req->d_dphi;
+    a.dq = req->d_dq;
+    a.score = req->d_score;
+    a.grad = req->d_grad;
+    a.count = req->d_count;
+    a.opg = req->d_opg;
+    a.cusum = req->d_cusum;
+    MK_HIP(timing_start(ctx, 1));
+    // a cell that is not observed keeps an all-zero slot: innov_step_kernel writes the observed ones only
+    MK_HIP(hipMemsetAsync(tape, 0, sizeof(double) * (size_t)(B * p->T * p->N * gs), ctx->stream));
+    MK_HIP(mk::launch_innov_step(g, ctx->stream));
+    MK_HIP(mk::launch_score_tangent(a, ctx->stream));
+    MK_HIP(mk::launch_score_stats(a, ctx->stream));
+    MK_HIP(timing_stop(ctx, 1)); // reported in the smoother slot of mk_last_kernel_ms / mk_kernel_ms_totals
     return MK_OK;
 }
 

@@ -14,7 +14,7 @@ import logging
 import numpy as np
 
 from . import _lib
-from ._lib import ForecastRequest, FunctionalRequest, MetranHipError, Outputs, Problem, RegressionRequest, WeightsRequest, check
+from ._lib import ForecastRequest, FunctionalRequest, MetranHipError, Outputs, Problem, RegressionRequest, ScoresRequest, WeightsRequest, check
 
 logger = logging.getLogger(__name__)
 
@@ -709,9 +709,9 @@ class BatchedKalman:
         return res
 
     # ------------------------------------------------------------------ the record readers: one scaffold
-    # loo_predict, disturbances, innovations, forecast, observation_weights, regression and functionals (which also runs the smoother) run the recording forward pass into a workspace ("_work") and one kernel
+    # loo_predict, disturbances, innovations, forecast, observation_weights, regression, scores and functionals (which also runs the smoother) run the recording forward pass into a workspace ("_work") and one kernel
     # that reads its filtered records.  NOTE: loo_supported() and disturbances_supported() are methods, innovations_supported and
-    # forecast_supported / observation_weights_supported / regression_supported / functionals_supported properties -- an inconsistency of the public API that is kept.
+    # forecast_supported / observation_weights_supported / regression_supported / scores_supported / functionals_supported properties -- an inconsistency of the public API that is kept.
     def _reader_stride(self, fn, specialised_only, refusal=None):
         """Doubles per (instance, step) of a record reader's workspace, the C ABI's ``fn(N, K)``; where the shape is not served
         0, or with ``refusal`` (a text with places for N and K) a MetranHipError."""
@@ -1111,6 +1111,88 @@ class BatchedKalman:
                                     ctypes.byref(req), self._p(res["status"])))
         self._mask_bad_instances(res, ("beta", "cov", "gain", "normal"))
         return res
+
+    # ------------------------------------------------------------------ per-step scores by the tangent filter
+    _SCORE_OUTPUTS = ("score", "grad", "count", "opg", "cusum")
+
+    @property
+    def scores_supported(self):
+        """True when ``scores`` serves this engine (C ABI ``mk_scores_work_stride`` > 0): N + K <= 64, specialised or
+        size-generic kernels alike, full-square records."""
+        return not self.packed_sym and self._reader_stride(self._L.mk_scores_work_stride, False) > 0
+
+    def _scores_stride(self):
+        if self.packed_sym:
+            raise MetranHipError("libmetran_hip error -2 (MK_ERR_SHAPE): the scores read full-square records; this engine was "
+                                 "created with packed_sym=True")
+        return self._reader_stride(self._L.mk_scores_work_stride, False,
+                                   "per-step scores serve shapes with N + K <= 64; (N=%s, K=%s) is not one")
+
+    def _scores_shapes(self, B):
+        """name -> (logical shape, follows the engine's layout) of the float64 buffers of ``scores``."""
+        n = self.n
+        shapes = self._bt_shapes(B, _work=self._scores_stride(), score=n)
+        shapes.update(grad=((B, n), False), opg=((B, n, n), False), cusum=((B, n, n), False))
+        return shapes
+
+    def alloc_scores(self, B):
+        """Buffers of ``scores`` for B instances (the forward pass's workspace with the gain tape and the innovations + the
+        outputs), for callers that run it repeatedly (pass them back as ``buffers=``)."""
+        torch = _torch()
+        res = self._reader_buffers(None, self._scores_shapes(B), "alloc_scores", sep=", ")
+        res["count"] = torch.empty(B, dtype=torch.int64, device=self.device)
+        return res
+
+    def scores(self, phi, q, dphi, dq, t_first=1, x0=None, P0=None, buffers=None):
+        """PER-STEP SCORES for B instances (C ABI ``mk_scores``; the forward-mode, tangent filter): ``score[b,t,p]`` is the
+        derivative of step t's contribution to -2 log L, ``sum_j (log f + v^2 / f)`` over the cells observed at t, with respect to
+        parameter p -- one per state, moving ``phi_p`` by ``dphi[b,p]`` and ``q_p`` by ``dq[b,p]`` (the chain rule to the caller's
+        parameters stays outside; ``scores_alpha`` is Metran's).  What statsmodels calls ``score_obs``.  A step is counted when
+        ``t >= t_first`` and it holds an observation.  Returns a dict with ``score [B,T,n]`` (zero at an empty step; stored for
+        t < t_first too), ``grad [B,n]`` (the sum over the counted steps), ``count [B]`` (their number m), ``opg [B,n,n]`` =
+        ``sum s_t s_t'`` (an information matrix that is positive semi-definite by construction), ``cusum [B,n,n]`` =
+        ``sum S_t S_t'`` with ``S_t = sum_{u <= t} (s_u - grad / m)`` (the tied-down cumulative scores of the Nyblom-Hansen test:
+        ``metran_amd.scores.nyblom``) and ``status`` (the filter's MK_FLAG_* bits); the rows of an instance whose status carries
+        ``FLAG_NONPOSITIVE_F`` are NaN.  Five launches (the recording forward pass, a clear, the gain writer, the tangent kernel,
+        the sums); an instance's outputs do not depend on the batch, bit for bit."""
+        torch = _torch()
+        t_first = int(t_first)
+        if t_first < 0:
+            raise ValueError("t_first must be >= 0")
+        self._scores_stride()
+        prob, keep, B = self._problem(phi, q, 0, x0, P0)
+        dphi, dq = self._dev(dphi, (B, self.n), "dphi").contiguous(), self._dev(dq, (B, self.n), "dq").contiguous()
+        res = self._reader_buffers(buffers, self._scores_shapes(B), "alloc_scores", sep=", ")
+        t = res.get("count")
+        if buffers is None:
+            t = res["count"] = torch.empty(B, dtype=torch.int64, device=self.device)
+        if t is None or tuple(t.shape) != (B,) or t.dtype != torch.int64 or not t.is_contiguous():
+            raise ValueError("buffers['count'] must be a contiguous int64 tensor of shape (%d,) (alloc_scores)" % B)
+        req = ScoresRequest()
+        req.d_dphi, req.d_dq, req.t_first = dphi.data_ptr(), dq.data_ptr(), t_first
+        for key in self._SCORE_OUTPUTS:
+            setattr(req, "d_" + key, res[key].data_ptr())
+        self._bind_stream()
+        check(self._L.mk_scores(self._ctx, ctypes.byref(prob), self._p(res["_work"]), 1 if self.time_major else 0,
+                                ctypes.byref(req), self._p(res["status"])))
+        self._mask_bad_instances(res, ("score", "grad", "opg", "cusum"))
+        return res
+
+    def scores_alpha(self, alpha, dt=1.0, t_first=1):
+        """``scores`` for Metran's parametrisation: ``phi, q`` by ``params_from_alpha`` and the derivatives with respect to alpha,
+        ``dphi = phi dt / alpha^2`` and ``dq = -2 phi dphi c`` with c = 1 - communality for a series and 1 for a factor."""
+        torch = _torch()
+        alpha = self._dev(alpha)
+        if alpha.ndim == 1:
+            alpha = alpha[None]
+        phi, q = self.params_from_alpha(alpha, dt=dt)
+        B = int(alpha.shape[0])
+        if B % self.R != 0:
+            raise ValueError("number of instances B=%d must be a multiple of the number of records R=%d" % (B, self.R))
+        c = torch.cat([1.0 - (self.loadings * self.loadings).sum(2), torch.ones((self.R, self.K), dtype=torch.float64, device=self.device)], 1)
+        dphi = phi * float(dt) / (alpha * alpha)
+        dq = -2.0 * phi * dphi * c.repeat(B // self.R, 1)
+        return self.scores(phi, q, dphi, dq, t_first=t_first)
 
     # ------------------------------------------------------------------ exact window means, changes and contrasts
     @property
