@@ -108,7 +108,9 @@ def shared_group(N, K, T, R, S, seed, patterns=MISSINGNESS, usable=_usable):
     """R records and B = S * R instances in the library's order (instance s * R + r reads record r).  dict: obs [R,T,N],
     loadings [R,N,K], obsvar / scale / offset [R,N], patterns [R]; phi / q / x0 [B,n], P0 [B,n,n]; N, K, T, R, S, B.
     ``patterns`` / ``usable``: the missingness patterns taken in turn and the condition a drawn record is redrawn until it
-    meets (tests/time_axis.py has its own: it edits the records afterwards)."""
+    meets (tests/time_axis.py has its own: it edits the records afterwards).  MILD by construction: a record is redrawn until
+    every persistence is below 1 - 1e-3, so that flat bars apply; the hard models (tests/hard_models.py) go through the routes
+    that use these groups in tests/test_gpu_property*.py."""
     rng = np.random.default_rng([int(seed), N, K, T, R, S])
     n, B = N + K, S * R
     g = dict(N=N, K=K, T=T, R=R, S=S, B=B, obs=np.empty((R, T, N)), loadings=np.empty((R, N, K)), patterns=[])

@@ -2,7 +2,9 @@
 tests/test_gpu_property.py and, on the CPU, by tests/test_property_generator.py, which runs the SAME sweep through the oracle
 and the numpy restatements so that every tolerance below is known to hold between two independent implementations before
 a GPU minute is spent on it; the diagnostic routes -- disturbances, forecasts, observation weights, draws -- take the same
-sweep in tests/test_gpu_property_diagnostics.py / tests/test_property_diagnostics.py, with the bars at the end of this file).
+sweep in tests/test_gpu_property_diagnostics.py / tests/test_property_diagnostics.py, the fitting routes -- intervention effects,
+window functionals, per-step scores -- in tests/test_gpu_property_fits.py / tests/test_property_fits.py, with the bars at the end of
+this file).
 
 A group = B models of one shape (N, K) and one length T (a launch needs a common T), each model drawn independently:
   persistence   phi = exp(-1/alpha), alpha ~ U(2, 60) (Metran's parametrisation, metran.py:246-263); in 30 % of the models one
@@ -220,6 +222,11 @@ DRAW_TOL = 1e-9         # tests/test_draws_gpu.py::TOL, the smoothed-moment bar:
 PERTURB_TOL = 1e-11     # tests/test_draws_gpu.py::PERTURB_TOL
 # the last line of scripts/measure_diagnostic_bars.py (31 sweeps, 10 912 models):
 MEASURED = {"dist_r": 0.43, "dist_n": 2.1, "forecast_mean": 0.18, "forecast_var": 0.62, "weights_series": 0.47, "weights_states": 0.86}
+# ... and of its run with the fitting routes (the same 31 sweeps; those routes on the 279 compared models of the default sweep and,
+# for the 30 further seeds, on the compared models of the shapes up to N + K = 22: 7 612 more for the regression, 7 212 for the scores),
+# each figure the printed one rounded UP.  The score figures are not of order one: see ``score_tolerances``.
+MEASURED.update({"regress_normal": 3.5, "regress_beta": 46.0, "regress_cov": 0.31, "regress_gain": 7.8,
+                 "score_score": 4.9e3, "score_grad": 1.7e3, "score_opg": 5.4e4, "score_cusum": 2.1e2})
 
 
 def _top(a):
@@ -271,3 +278,89 @@ def draw_tolerance(g, b, ref_star, xplus, what="series"):
     loadings has at most unit length)."""
     rows = float((1.0 + np.abs(g["loadings"][b]).sum(1)).max()) if what == "series" else 1.0
     return rows * (smoother_tolerance(g, b, ref_star) + PERTURB_TOL * _top(xplus))
+
+
+# ------------------------------------------------------------------ the fitting routes' bars (regression, functionals, scores)
+REGRESS_BAR_A = max(16 * 1.31e-14, 1e-13)     # tests/test_regression_gpu.py::BAR_A (16 x measured, the floor of 1e-13)
+REGRESS_BAR_S = max(16 * 1.07e-13, 1e-13)     # tests/test_regression_gpu.py::BAR_S
+FUNCTIONAL_ATOL = 1e-9                        # tests/call_forms.py::SMOOTH_ATOL: smoother_tolerance's flat part
+SCORE_SHORT = 2                               # tests/test_scores_gpu.py::SHORT: records of up to two steps have bars of their own
+SCORE_BAR = {"score": max(16 * 2.11e-14, 1e-13), "grad": max(16 * 4.96e-15, 1e-13), "opg": max(16 * 8.78e-15, 1e-13),
+             "cusum": max(16 * 1.01e-16, 1e-13)}                                     # tests/test_scores_gpu.py::BAR
+SCORE_BAR_SHORT = {"score": max(16 * 1.16e-14, 1e-13), "grad": max(16 * 8.75e-14, 1e-13), "opg": max(16 * 9.88e-14, 1e-13),
+                   "cusum": max(16 * 2.78e-16, 1e-13)}                               # tests/test_scores_gpu.py::BAR_SHORT
+
+
+def score_tolerances(g, b, ref, T, margin=MARGIN):
+    """{"score", "grad", "opg", "cusum"}: the bar of score_ref.differences -- a difference relative to score_ref's own scale (the
+    output's expression with every term replaced by its absolute value) -- of model b against score_ref.scores in longdouble;
+    ``T``: the record's length (up to SCORE_SHORT steps the flat part is the short records').  The scales are score_ref's, raised
+    where Metran's chain rule makes the prediction's tangent term cancel (tests/diagnostic_sweep.py::_floored).
+    Measured, float64 against longdouble restatement in units of conditioning * scale, default sweep / seeds 1-10, 11-20, 21-30:
+    score 0.733 / 4.71e3, 4.89e3, 2.5e3 (the largest at seed 20, (3,1) T = 39, "iid", min q 4.9e-9); grad 0.436 / 1.48e3, 1.01e3,
+    1.61e3; opg 22.6 / 3.23e4, 3.68e3, 5.38e4; cusum 0.0369 / 83.6, 52.2, 205 (these three largest at seed 23, (3,1) T = 8, "last",
+    min q 1.8e-9).  The largest gaps themselves: 1.3e-3 (score: seed 8, (3,1) T = 49, "first", min q 2.3e-9), 5.0e-4 (grad), 1.7e-2
+    (opg), 6.3e-5 (cusum: all seed 23).  These are NOT multiples of order one, as every other route's are: on the default sweep the
+    tangent filter stays below 0.74 of the conditioning (22.6 for opg, whose scale sum_t scale(s_t) scale(s_t)' is small where the
+    large steps of two parameters are different steps -- a "heavy" record), but at models of the further seeds with min q of a few 1e-9
+    a correct float64 evaluation of fd / f - v^2 fd / f^2 loses a thousand times more than the filter underneath it
+    loses -- the loss grows faster than 1 / min q.  The bar follows the measurement (the form allows nothing else), so on a model
+    with q ~ 2e-9 it is about 6e-3 of the scale, while at min q >= 1e-6 (conditioning 1e-9 and below) it stays under 2e-5 (score)
+    and every wrong variant is still outside it in every group (tests/test_property_fits.py)."""
+    c = conditioning(g, b, ref)
+    flat = SCORE_BAR_SHORT if T <= SCORE_SHORT else SCORE_BAR
+    return {k: flat[k] + margin * MEASURED["score_" + k] * c for k in flat}
+
+
+def regression_scales(reg):
+    """The scales of a regression result (``reg``: regress_ref.regression in longdouble): ``normal [M+1,M+1]`` sqrt(|A_pp| |A_qq|)
+    (1 where it is zero), ``beta [M]`` the standard errors and ``cov [M,M]`` se_i se_j of the kept effects (NaN at a dropped one),
+    ``gain`` the gain's own expression sum_i beta_i s_i, s = A[1:,0], with every term replaced by its absolute value (1 where
+    nothing is kept), ``cond`` regress_ref.unit_condition of the kept effects."""
+    import regress_ref
+
+    A = np.abs(np.asarray(reg["normal"], dtype=np.float64))
+    dg = np.sqrt(np.diag(A))
+    normal = np.outer(dg, dg)
+    normal[normal == 0] = 1.0
+    cov = np.asarray(reg["cov"], dtype=np.float64)
+    se = np.sqrt(np.diag(cov))
+    kept = ~np.asarray(reg["dropped"])
+    gain = float((np.abs(np.asarray(reg["beta"], dtype=np.float64)) * A[1:, 0])[kept].sum()) if kept.any() else 0.0
+    return dict(normal=normal, beta=se, cov=np.outer(se, se), gain=gain if gain > 0 else 1.0,
+                cond=regress_ref.unit_condition(reg["normal"], reg["dropped"]))
+
+
+def regression_tolerances(g, b, ref, reg, margin=MARGIN):
+    """{"normal" [M+1,M+1], "beta" [M], "cov" [M,M], "gain"}: absolute bars of model b against regress_ref.regression in longdouble
+    (``reg``: that reference), each (flat + margin * MEASURED * conditioning) * ``regression_scales``; the flat parts are the
+    regression tier's BAR_A (normal matrix) and BAR_S (the rest).  For beta and cov the conditioning is multiplied by the condition
+    number of the unit-diagonal S of the kept effects (``cond``, up to 9.5e8 on the sweep's effect lists: a level shift and a ramp on
+    one series of a two-step record are nearly collinear).
+    Measured, float64 against longdouble restatement in units of conditioning * scale (beta, cov: * cond), default sweep / seeds
+    1-10, 11-20, 21-30: normal 0.218 / 0.597, 3.5, 0.871 (the largest at seed 17, (7,2) T = 2, "iid"); beta 0.315 / 17.6, 45.3, 10.1
+    (seed 12, (2,1) T = 27, "series", min q 5.2e-8); cov 0.0807 / 0.258, 0.302, 0.137 (seed 12, (7,2) T = 2, "series"); gain 0.543 /
+    3.72, 7.61, 7.76 (seed 23, (4,1) T = 2, "iid").  Largest gaps: 7.5e-9 (normal), 4.9e-6 of a standard error (beta: seed 8, (3,1)
+    T = 49, "first", min q 2.3e-9), 5.1e-9 (cov), 2.6e-8 (gain).  The factor cond is borne out for the ordinary models and not
+    needed for the hard ones: WITHOUT it the ratios are 0.65 (beta) and 0.625 (cov) on the default sweep but 2.9e4 and 5.5e4 beyond
+    it, both at two-step records of ordinary models whose cond is 1e6 to 1e9 -- among the models whose conditioning exceeds 1e-10
+    beta is at most 82 without the factor and 45.3 with it.  So it stays.  All of this holds for the models that meet
+    tests/diagnostic_sweep.py::regression_usable (a dropped set that does not hang on rounding); the others leave beta and cov."""
+    c = conditioning(g, b, ref)
+    sc = regression_scales(reg)
+    solve = margin * c * sc["cond"]
+    return dict(normal=(REGRESS_BAR_A + margin * MEASURED["regress_normal"] * c) * sc["normal"],
+                beta=(REGRESS_BAR_S + MEASURED["regress_beta"] * solve) * sc["beta"],
+                cov=(REGRESS_BAR_S + MEASURED["regress_cov"] * solve) * sc["cov"],
+                gain=(REGRESS_BAR_S + margin * MEASURED["regress_gain"] * c) * sc["gain"])
+
+
+def functional_tolerances(g, b, ref, reach):
+    """(atol of the mean, atol of the variance) [W,C] of the window functionals of model b against functional_ref.functional_walk
+    in longdouble from the ORACLE's records.  The kernel walks its OWN filtered and smoothed records, so its bar is the smoother's
+    bar of this model, ``smoother_tolerance`` (flat part FUNCTIONAL_ATOL), carried through the functional as functional_ref.bars
+    carries it: times ``reach`` = A zeta for the mean and (A zeta)^2 for the variance (tests/diagnostic_sweep.py::functional_reach).
+    Nothing is measured here: two existing bars combined, as ``draw_tolerance``.  What the walk itself loses in float64 is recorded
+    by scripts/measure_diagnostic_bars.py: at most 2.7e-7 (mean) and 6.3e-7 (variance) of this bar over the 31 sweeps (7 891 models)."""
+    tol = smoother_tolerance(g, b, ref)
+    return tol * reach, tol * reach * reach

@@ -77,9 +77,11 @@ def normal(y, phi, G, gain, effects, t_first=1, x0=None, dtype=np.longdouble, de
     return A, support
 
 
-def solve(A, support, used=None, dtype=np.longdouble):
+def solve(A, support, used=None, dtype=np.longdouble, pivots=None):
     """(beta [M], cov [M,M], gain, dropped [M] bool) from the augmented normal matrix: S = A[1:,1:] to unit diagonal, Cholesky in
-    effect order, an effect with support 0 (or not ``used``) or a pivot below MIN_PIVOT dropped, the rest solved without it."""
+    effect order, an effect with support 0 (or not ``used``) or a pivot below MIN_PIVOT dropped, the rest solved without it.
+    ``pivots``: a list that receives the M unit-diagonal pivots as they are met (NaN for an effect that is out before its pivot is
+    looked at: unused, no support or a zero diagonal)."""
     A = np.asarray(A, dtype=dtype)
     M = A.shape[0] - 1
     used = np.ones(M, dtype=bool) if used is None else np.asarray(used, dtype=bool)
@@ -94,6 +96,8 @@ def solve(A, support, used=None, dtype=np.longdouble):
     ss = np.array([s[i] / sd[i] for i in range(M)], dtype=dtype)
     for k in range(M):                                             # right-looking, row by row below the pivot
         piv = U[k, k]
+        if pivots is not None:
+            pivots.append(float(piv) if keep[k] else float("nan"))
         keep[k] = bool(keep[k] and piv >= MIN_PIVOT)
         lk = np.sqrt(piv) if keep[k] else one
         U[k, k] = lk
@@ -145,13 +149,14 @@ def solve(A, support, used=None, dtype=np.longdouble):
 
 
 def regression(y, phi, q, G, R=None, x0=None, P0=None, effects=(), t_first=1, dtype=np.longdouble, gain=None, **wrong):
-    """dict of one model: ``beta, cov, gain, normal, support, dropped`` (dropped as a bool array [M]).  ``gain``: the dict of
-    ``weights_ref.gains`` computed before, in the same dtype."""
+    """dict of one model: ``beta, cov, gain, normal, support, dropped`` (dropped as a bool array [M]) and ``pivots`` (``solve``).
+    ``gain``: the dict of ``weights_ref.gains`` computed before, in the same dtype."""
     effects = np.asarray(effects, dtype=np.int64).reshape(-1, 4)
     g_ = gain if gain is not None else weights_ref.gains(y, phi, q, G, R, x0, P0, dtype)
     A, support = normal(y, phi, G, g_, effects, t_first, x0, dtype, **wrong)
-    beta, cov, gn, dropped = solve(A, support, effects[:, 0] >= 0, dtype)
-    return {"beta": beta, "cov": cov, "gain": gn, "normal": A, "support": support, "dropped": dropped}
+    pivots = []
+    beta, cov, gn, dropped = solve(A, support, effects[:, 0] >= 0, dtype, pivots)
+    return {"beta": beta, "cov": cov, "gain": gn, "normal": A, "support": support, "dropped": dropped, "pivots": np.array(pivots)}
 
 
 def adjusted(y, effects, beta):

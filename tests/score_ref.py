@@ -133,6 +133,7 @@ def scores(y, phi, q, G, R=None, x0=None, P0=None, dphi=None, dq=None, t_first=1
     out, scale = sums(score, sscale, counted, dtype, uncentred)
     out["score"] = score
     scale["score"] = np.broadcast_to(sscale.max(axis=0) if T else np.zeros(n, dtype=dtype), (T, n)).copy()
+    scale["steps"], scale["counted"] = sscale, counted             # every step's own scale: what the four scales are made of
     out["scale"] = scale
     return out
 

@@ -6,7 +6,11 @@ stays 6.6e-6 of a bar from the definition, so the bars stand as given -- bit for
 both layouts and kernel families, next to invalid models, and the refusals of the raw ABI.
 
 Measured on the MI355X: the largest distance on any case of this file is 6.8e-6 of a bar ((8,2), T = 17; printed per case with
-``-s``); the file's 31 tests take 20 s."""
+``-s``); the file's 31 tests take 20 s.
+
+The models here are MILD by construction: the records come from call_forms.shared_group, which redraws until every persistence is
+below 1 - 1e-3.  Persistence up to 1 - 1e-9, a communality of 0.999 and the hard missingness patterns are run through this route
+by tests/test_gpu_property_fits.py (tests/test_property_fits.py on the CPU), at the conditioning-aware bars of tests/hard_models.py."""
 import ctypes
 
 import numpy as np

@@ -16,7 +16,12 @@ at most 1e4 on every input (tests/test_regression_host.py checks the cap; the la
 Counting convention of the checks against the filter: mk_regression counts the cells of the steps t >= t_first, the filter's
 warm-up (get_mle, metran/kalmanfilter.py:550-567) skips the first ``warmup`` steps THAT HOLD AN OBSERVATION.  The two name the same
 cells when warmup = the number of non-empty steps before t_first (``_warmup_of``), which is what the comparisons use: the
-records of the data pattern begin with empty steps."""
+records of the data pattern begin with empty steps.
+
+The models here are MILD by construction (``test_weights_gpu._data``: 40 % missing cells, ordinary persistence, P0 near the
+identity; effect lists whose unit-diagonal condition number stays below 1e4).  Persistence up to 1 - 1e-9, a communality of 0.999,
+records with one observation or a never-observed series and nearly collinear effects are run through this route by
+tests/test_gpu_property_fits.py (tests/test_property_fits.py on the CPU), at the conditioning-aware bars of tests/hard_models.py."""
 import ctypes
 
 import numpy as np

@@ -23,7 +23,12 @@ Over 17 and 40 steps the same errors are 5e-15 of the sum's scale.
 
 Counting convention of the checks against the adjoint gradient: mk_scores counts the steps t >= t_first that hold an observation,
 the filter's warm-up skips the first ``warmup`` steps that hold one.  The two name the same steps when warmup = the number of
-non-empty steps before t_first (``_warmup_of``, as in tests/test_regression_gpu.py)."""
+non-empty steps before t_first (``_warmup_of``, as in tests/test_regression_gpu.py).
+
+The models here are MILD by construction (``test_weights_gpu._data``: 40 % missing cells, ordinary persistence, P0 near the
+identity), which is what the flat bars above are for.  Persistence up to 1 - 1e-9, a communality of 0.999 and the hard missingness
+patterns are run through this route, with Metran's own chain rule for (dphi, dq), by tests/test_gpu_property_fits.py
+(tests/test_property_fits.py on the CPU), at the conditioning-aware bars of tests/hard_models.py."""
 import ctypes
 
 import numpy as np
