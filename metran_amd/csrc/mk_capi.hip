@@ -241,6 +241,77 @@ static void fill_layout(Args &a, int time_major, int64_t B, int64_t T) // block 
     a.bs = time_major ? 1 : T;
     a.ts = time_major ? B : 1;
 }
+template <class Args>
+static auto fill_shape(Args &a, const mk_problem *p, int) -> decltype((void)a.K) // the blocks that carry N and K
+{
+    a.N = (int)p->N;
+    a.K = (int)p->K;
+}
+template <class Args>
+static void fill_shape(Args &, const mk_problem *, long) {}
+template <class Args>
+static auto fill_records(Args &a, const double *d_work, int64_t rs, int) -> decltype((void)a.F) // the blocks that read the records
+{
+    a.rs = rs;
+    a.F = d_work;
+}
+template <class Args>
+static void fill_records(Args &, const double *, int64_t, long) {}
+
+// What the kernel block of every record reader starts from: zeroed, then the problem, the initial moments, the layout, the filtered
+// records of rs doubles that the recording forward pass left at the head of d_work, and N and K where the block has them.
+template <class Args>
+static Args reader_args(const mk_problem *p, const double *d_work, int64_t rs, int time_major)
+{
+    Args a;
+    memset(&a, 0, sizeof(a));
+    fill_model(a, p);
+    fill_initial(a, p);
+    fill_layout(a, time_major, p->n_instances, p->T);
+    fill_shape(a, p, 0);
+    fill_records(a, d_work, rs, 0);
+    return a;
+}
+
+// ---- the workspace d_work of the record readers: the one place that knows its format.  The filtered records of B * T steps are
+// packed at the head; behind them, each for all B * T steps, the regions of the reader's kind: the gain tape (N slots of gs doubles
+// per step) and behind it the scores' row of N innovations, the forecast skill's partial sums, or the smoothed records.
+// (mk_loo's wide branch is no record reader: its d_work is the tape of MK_OUT_TAPE.) ----
+enum work_kind { WORK_RECORDS, WORK_FORECAST, WORK_GAIN, WORK_SCORES, WORK_FUNCTIONALS };
+struct work_layout {
+    int64_t rs, gs;                         // doubles per record and per gain slot (0: no tape)
+    int64_t stride;                         // doubles per (instance, step) of the whole workspace: what mk_*_work_stride returns
+    int64_t tape, innov, partial, smoothed; // where each region starts, in doubles from d_work (0: the kind has none)
+};
+static work_layout layout_of(work_kind kind, int64_t N, int64_t K, int64_t B = 0, int64_t T = 0)
+{
+    work_layout w = {};
+    w.rs = w.stride = mk::record_stride((int)(N + K));
+    const auto region = [&](int64_t doubles_per_step) {
+        const int64_t at = B * T * w.stride;
+        w.stride += doubles_per_step;
+        return at;
+    };
+    if (kind == WORK_GAIN || kind == WORK_SCORES) {
+        w.gs = mk::weights_slot_stride(N + K);
+        w.tape = region(N * w.gs);
+    }
+    if (kind == WORK_SCORES) w.innov = region(N);
+    if (kind == WORK_FORECAST) w.partial = region(mk::forecast_partial_stride(N));
+    if (kind == WORK_FUNCTIONALS) w.smoothed = region(w.rs);
+    return w;
+}
+
+// The launches of a record reader behind its forward pass, timed as one: reported in the smoother slot of mk_last_kernel_ms /
+// mk_kernel_ms_totals (for mk_functionals beside the smoother's own launch).
+template <class Launches>
+static int timed_launches(mk_context *ctx, Launches launches)
+{
+    MK_HIP(timing_start(ctx, 1));
+    if (int rc = launches()) return rc;
+    MK_HIP(timing_stop(ctx, 1));
+    return MK_OK;
+}
 
 // Each buffer must end inside the device allocation it starts in (an interior pointer of a pooled allocation passes whenever the
 // pool's block is large enough -- the check catches a buffer that is too small, not every misuse).
@@ -1099,17 +1170,17 @@ MK_API int mk_set_adjoint_updates(mk_context *ctx, double *d_buf, int64_t capaci
     return MK_OK;
 }
 
-// what every mode of the adjoint walks reads: the problem and the filtered records the recording forward pass left in d_work
-static mk::AdjointArgs adjoint_walk_args(const mk_problem *p, const double *d_work, int64_t record_stride, int time_major)
+// The opening checks of the entry points that take a request struct, in this order: the context, too many states (refused first:
+// every other shape that the entry point's work stride does not serve is one check_problem refuses), the problem, the request, d_work.
+static int reader_preamble(mk_context *ctx, const char *who, const char *request_type, const mk_problem *p, int max_states,
+                           const void *req, const double *d_work)
 {
-    mk::AdjointArgs a;
-    memset(&a, 0, sizeof(a));
-    fill_model(a, p);
-    fill_initial(a, p);
-    fill_layout(a, time_major, p->n_instances, p->T);
-    a.rs = record_stride;
-    a.F = d_work;
-    return a;
+    MK_CTX(ctx);
+    if (p && p->N >= 1 && p->K >= 1 && p->N + p->K > max_states) return too_many_states(who, p, max_states);
+    if (int rc = check_problem(p)) return rc;
+    if (!req) return fail(MK_ERR_INVALID, "%s: null %s", who, request_type);
+    if (!d_work) return fail(MK_ERR_INVALID, "%s: d_work is required", who);
+    return MK_OK;
 }
 
 // The recording forward pass every record reader starts with: filtered records only (+ the per-step bookkeeping in the record
@@ -1131,6 +1202,21 @@ static int record_pass(mk_context *ctx, const mk_problem *p, double *d_work, int
     o.time_major = time_major;
     o.record_stride = record_stride;
     return do_filter(ctx, p, &o);
+}
+
+// The gain-tape stage of the weights, the regression and the scores, inside the caller's timed launches: innov_step_kernel
+// writes the gains of every observed cell behind the records (and, for the scores, the innovations behind the tape).
+static int gain_tape_stage(mk_context *ctx, const mk_problem *p, double *d_work, const work_layout &w, int time_major,
+                           double *d_innov = nullptr)
+{
+    mk::InnovArgs g = reader_args<mk::InnovArgs>(p, d_work, w.rs, time_major);
+    g.v = d_innov;
+    g.gain = d_work + w.tape;
+    g.gs = w.gs;
+    // a cell that is not observed keeps an all-zero slot: innov_step_kernel writes the observed ones only
+    MK_HIP(hipMemsetAsync(g.gain, 0, sizeof(double) * (size_t)(p->n_instances * p->T * p->N * w.gs), ctx->stream));
+    MK_HIP(mk::launch_innov_step(g, ctx->stream));
+    return MK_OK;
 }
 
 MK_API int mk_loglik_grad(mk_context *ctx, const mk_problem *p, double *d_work, int time_major, double *d_mle,
@@ -1167,24 +1253,24 @@ MK_API int mk_loglik_grad_phases(mk_context *ctx, const mk_problem *p, double *d
         if (rc) return rc;
     }
     if (!(phases & MK_GRAD_BACKWARD)) return MK_OK;
-    mk::AdjointArgs a = adjoint_walk_args(p, d_work, rs, time_major);
+    mk::AdjointArgs a = reader_args<mk::AdjointArgs>(p, d_work, rs, time_major);
     a.upd = upd;
     a.us = upd ? us : 0;
     a.warmup = p->warmup;
     a.sigmacount = (const long long *)d_sigmacount;
     a.gphi = d_gphi;
     a.gq = d_gq;
-    MK_HIP(timing_start(ctx, 1));
-    MK_HIP(dispatch_adjoint((int)p->N, (int)p->K, a, ctx->stream));
-    MK_HIP(timing_stop(ctx, 1)); // reported in the smoother slot of mk_last_kernel_ms / mk_kernel_ms_totals
-    return MK_OK;
+    return timed_launches(ctx, [&]() -> int {
+        MK_HIP(dispatch_adjoint((int)p->N, (int)p->K, a, ctx->stream));
+        return MK_OK;
+    });
 }
 
 // ---- leave-one-out predictions (de Jong's deletion result on the two backward walks) ----
 MK_API int64_t mk_loo_work_stride(int64_t N, int64_t K)
 {
     if (N < 1 || K < 1 || !specialised(N, K)) return 0;
-    if (N + K <= 16) return mk::record_stride((int)(N + K));
+    if (N + K <= 16) return layout_of(WORK_RECORDS, N, K).stride;
     return mk_tape_supported(N, K) ? mk::tape_stride_c((int)N, (int)K) : 0;
 }
 
@@ -1206,14 +1292,14 @@ MK_API int mk_loo(mk_context *ctx, const mk_problem *p, double *d_work, int time
     if (int rc = buffers_fit("mk_loo", bufs, 3)) return rc;
     if (p->N + p->K <= 16) { // the recording forward pass, then the adjoint walk in its LOO mode
         if (int rc = record_pass(ctx, p, d_work, ws, time_major, d_status)) return rc;
-        mk::AdjointArgs a = adjoint_walk_args(p, d_work, ws, time_major);
+        mk::AdjointArgs a = reader_args<mk::AdjointArgs>(p, d_work, ws, time_major);
         a.loo_means = d_loo_means;
         a.loo_vars = d_loo_vars;
         fill_scaling(a, p);
-        MK_HIP(timing_start(ctx, 1));
-        MK_HIP(dispatch_loo((int)p->N, (int)p->K, &a, nullptr, ctx->stream));
-        MK_HIP(timing_stop(ctx, 1));
-        return MK_OK;
+        return timed_launches(ctx, [&]() -> int {
+            MK_HIP(dispatch_loo((int)p->N, (int)p->K, &a, nullptr, ctx->stream));
+            return MK_OK;
+        });
     }
     // wide models: the tape writer of the projection, then the tape walk in its LOO mode
     mk_outputs o;
@@ -1243,10 +1329,10 @@ MK_API int mk_loo(mk_context *ctx, const mk_problem *p, double *d_work, int time
     a.q = p->d_q;
     a.F = d_work;
     a.status = d_status;
-    MK_HIP(timing_start(ctx, 1));
-    MK_HIP(dispatch_loo((int)p->N, (int)p->K, nullptr, &a, ctx->stream));
-    MK_HIP(timing_stop(ctx, 1));
-    return MK_OK;
+    return timed_launches(ctx, [&]() -> int {
+        MK_HIP(dispatch_loo((int)p->N, (int)p->K, nullptr, &a, ctx->stream));
+        return MK_OK;
+    });
 }
 
 // ---- simulation smoother (Durbin & Koopman 2002): the unconditional paths and the perturbed records (draw_kernels.hip) ----
@@ -1426,7 +1512,7 @@ MK_API int mk_ensemble_summary(mk_context *ctx, int64_t S, int64_t cells, const 
 MK_API int64_t mk_disturbance_work_stride(int64_t N, int64_t K)
 {
     if (N < 1 || K < 1 || N + K > 64 || !specialised(N, K)) return 0;
-    return mk::record_stride((int)(N + K));
+    return layout_of(WORK_RECORDS, N, K).stride;
 }
 
 MK_API int mk_disturbances(mk_context *ctx, const mk_problem *p, double *d_work, int time_major, double *d_r, double *d_ninfo,
@@ -1448,20 +1534,20 @@ MK_API int mk_disturbances(mk_context *ctx, const mk_problem *p, double *d_work,
     if (int rc = buffers_fit("mk_disturbances", bufs, 3)) return rc;
     // the recording forward pass (no update tape: the walk recomputes), then the walk
     if (int rc = record_pass(ctx, p, d_work, ws, time_major, d_status)) return rc;
-    mk::AdjointArgs a = adjoint_walk_args(p, d_work, ws, time_major);
+    mk::AdjointArgs a = reader_args<mk::AdjointArgs>(p, d_work, ws, time_major);
     a.dist_r = d_r;
     a.dist_n = d_ninfo;
-    MK_HIP(timing_start(ctx, 1));
-    MK_HIP(dispatch_disturb((int)p->N, (int)p->K, a, ctx->stream));
-    MK_HIP(timing_stop(ctx, 1)); // reported in the smoother slot of mk_last_kernel_ms / mk_kernel_ms_totals
-    return MK_OK;
+    return timed_launches(ctx, [&]() -> int {
+        MK_HIP(dispatch_disturb((int)p->N, (int)p->K, a, ctx->stream));
+        return MK_OK;
+    });
 }
 
 // ---- one-step-ahead innovations and their whiteness statistics (innov_kernels.hip) ----
 MK_API int64_t mk_innovations_work_stride(int64_t N, int64_t K)
 {
     if (N < 1 || K < 1 || N + K > mk::innov_max_states || !mk_shape_supported(N, K)) return 0;
-    return mk::record_stride((int)(N + K));
+    return layout_of(WORK_RECORDS, N, K).stride;
 }
 
 MK_API int mk_innovations(mk_context *ctx, const mk_problem *p, double *d_work, int time_major, double *d_v, double *d_f,
@@ -1483,24 +1569,16 @@ MK_API int mk_innovations(mk_context *ctx, const mk_problem *p, double *d_work, 
                                    {d_pred_vars, cells, "d_pred_vars (n_instances * T * N doubles)"}};
     if (int rc = buffers_fit("mk_innovations", bufs, 5)) return rc;
     if (int rc = record_pass(ctx, p, d_work, ws, time_major, d_status)) return rc;
-    mk::InnovArgs a;
-    memset(&a, 0, sizeof(a));
-    fill_model(a, p);
-    fill_initial(a, p);
+    mk::InnovArgs a = reader_args<mk::InnovArgs>(p, d_work, ws, time_major);
     fill_scaling(a, p);
-    fill_layout(a, time_major, p->n_instances, p->T);
-    a.N = (int)p->N;
-    a.K = (int)p->K;
-    a.rs = ws;
-    a.F = d_work;
     a.v = d_v;
     a.f = d_f;
     a.pred_mean = d_pred_means;
     a.pred_var = d_pred_vars;
-    MK_HIP(timing_start(ctx, 1));
-    MK_HIP(mk::launch_innov_step(a, ctx->stream));
-    MK_HIP(timing_stop(ctx, 1)); // reported in the smoother slot of mk_last_kernel_ms / mk_kernel_ms_totals
-    return MK_OK;
+    return timed_launches(ctx, [&]() -> int {
+        MK_HIP(mk::launch_innov_step(a, ctx->stream));
+        return MK_OK;
+    });
 }
 
 MK_API int mk_innovation_stats(mk_context *ctx, int64_t B, int64_t T, int64_t N, int time_major, int64_t t_first, int64_t nlags,
@@ -1535,18 +1613,13 @@ MK_API int64_t mk_forecast_max_horizon(void) { return mk::forecast_max_horizon; 
 MK_API int64_t mk_forecast_work_stride(int64_t N, int64_t K)
 {
     if (N < 1 || K < 1 || N + K > mk::forecast_max_states || !mk_shape_supported(N, K)) return 0;
-    return mk::record_stride((int)(N + K)) + mk::forecast_partial_stride(N);
+    return layout_of(WORK_FORECAST, N, K).stride;
 }
 
 MK_API int mk_forecast(mk_context *ctx, const mk_problem *p, double *d_work, int time_major, const mk_forecast_request *req,
                        uint32_t *d_status)
 {
-    MK_CTX(ctx);
-    // refused first: every other shape that mk_forecast_work_stride does not serve is one check_problem refuses
-    if (p && p->N >= 1 && p->K >= 1 && p->N + p->K > mk::forecast_max_states) return too_many_states("mk_forecast", p, mk::forecast_max_states);
-    if (int rc = check_problem(p)) return rc;
-    if (!req) return fail(MK_ERR_INVALID, "mk_forecast: null mk_forecast_request");
-    if (!d_work) return fail(MK_ERR_INVALID, "mk_forecast: d_work is required");
+    if (int rc = reader_preamble(ctx, "mk_forecast", "mk_forecast_request", p, mk::forecast_max_states, req, d_work)) return rc;
     const bool fan = req->d_fan_means || req->d_fan_vars, track = req->d_track_means || req->d_track_vars, skill = req->d_skill != nullptr;
     if (!fan && !track && !skill)
         return fail(MK_ERR_INVALID, "mk_forecast: nothing to write, give one of d_fan_means, d_fan_vars, d_track_means, d_track_vars, d_skill");
@@ -1559,9 +1632,9 @@ MK_API int mk_forecast(mk_context *ctx, const mk_problem *p, double *d_work, int
     if (req->t_first < 0) return fail(MK_ERR_INVALID, "mk_forecast: t_first must be >= 0");
     if (!(req->coverage_z > 0.0) || !std::isfinite(req->coverage_z))
         return fail(MK_ERR_INVALID, "mk_forecast: coverage_z must be positive and finite");
-    const int64_t ws = mk_forecast_work_stride(p->N, p->K);
-    const int64_t B = p->n_instances, rs = mk::record_stride((int)(p->N + p->K));
-    const device_buffer bufs[7] = {{d_work, B * p->T * ws, "d_work (n_instances * T * mk_forecast_work_stride(N, K) doubles)"},
+    const int64_t B = p->n_instances;
+    const work_layout w = layout_of(WORK_FORECAST, p->N, p->K, B, p->T);
+    const device_buffer bufs[7] = {{d_work, B * p->T * w.stride, "d_work (n_instances * T * mk_forecast_work_stride(N, K) doubles)"},
                                    {req->d_fan_origins, p->n_records, "d_fan_origins (n_records 64-bit integers)"},
                                    {req->d_fan_means, B * req->horizon * p->N, "d_fan_means (n_instances * horizon * N doubles)"},
                                    {req->d_fan_vars, B * req->horizon * p->N, "d_fan_vars (n_instances * horizon * N doubles)"},
@@ -1578,105 +1651,66 @@ MK_API int mk_forecast(mk_context *ctx, const mk_problem *p, double *d_work, int
                 return fail(MK_ERR_INVALID, "mk_forecast: d_fan_origins[%lld] = %lld is outside -1 .. T - 1 = %lld", (long long)r,
                             (long long)h[(size_t)r], (long long)(p->T - 1));
     }
-    // the records are packed at the head of d_work; the skill kernel's partial sums live behind them
-    if (int rc = record_pass(ctx, p, d_work, rs, time_major, d_status)) return rc;
-    mk::ForecastArgs a;
-    memset(&a, 0, sizeof(a));
-    fill_model(a, p);
-    fill_initial(a, p);
+    if (int rc = record_pass(ctx, p, d_work, w.rs, time_major, d_status)) return rc;
+    mk::ForecastArgs a = reader_args<mk::ForecastArgs>(p, d_work, w.rs, time_major);
     fill_scaling(a, p);
-    fill_layout(a, time_major, B, p->T);
-    a.N = (int)p->N;
-    a.K = (int)p->K;
     a.H = (int)req->horizon;
     a.track_h = track ? req->track_horizon : 1;
     a.t_first = req->t_first;
-    a.rs = rs;
     a.z2 = req->coverage_z * req->coverage_z;
-    a.F = d_work;
     a.fan_origins = req->d_fan_origins;
     a.fan_mean = req->d_fan_means;
     a.fan_var = req->d_fan_vars;
     a.track_mean = req->d_track_means;
     a.track_var = req->d_track_vars;
     a.skill = req->d_skill;
-    a.partial = d_work + B * p->T * rs;
-    MK_HIP(timing_start(ctx, 1));
-    if (fan || track) MK_HIP(mk::launch_forecast_path(a, ctx->stream));
-    if (skill) MK_HIP(mk::launch_forecast_skill(a, ctx->stream));
-    MK_HIP(timing_stop(ctx, 1)); // reported in the smoother slot of mk_last_kernel_ms / mk_kernel_ms_totals
-    return MK_OK;
+    a.partial = d_work + w.partial;
+    return timed_launches(ctx, [&]() -> int {
+        if (fan || track) MK_HIP(mk::launch_forecast_path(a, ctx->stream));
+        if (skill) MK_HIP(mk::launch_forecast_skill(a, ctx->stream));
+        return MK_OK;
+    });
 }
 
 // ---- observation weights of smoothed series and states (weights_kernels.hip) ----
 MK_API int64_t mk_weights_work_stride(int64_t N, int64_t K)
 {
     if (N < 1 || K < 1 || N + K > mk::weights_max_states || !mk_shape_supported(N, K)) return 0;
-    return mk::record_stride((int)(N + K)) + N * mk::weights_slot_stride(N + K);
+    return layout_of(WORK_GAIN, N, K).stride;
 }
 
 MK_API int mk_observation_weights(mk_context *ctx, const mk_problem *p, double *d_work, int time_major, const mk_weights_request *req,
                                   uint32_t *d_status)
 {
-    MK_CTX(ctx);
-    // refused first: every other shape that mk_weights_work_stride does not serve is one check_problem refuses
-    if (p && p->N >= 1 && p->K >= 1 && p->N + p->K > mk::weights_max_states)
-        return too_many_states("mk_observation_weights", p, mk::weights_max_states);
-    if (int rc = check_problem(p)) return rc;
-    if (!req) return fail(MK_ERR_INVALID, "mk_observation_weights: null mk_weights_request");
-    if (!d_work) return fail(MK_ERR_INVALID, "mk_observation_weights: d_work is required");
+    if (int rc = reader_preamble(ctx, "mk_observation_weights", "mk_weights_request", p, mk::weights_max_states, req, d_work)) return rc;
     if (!req->d_targets || !req->d_weights) return fail(MK_ERR_INVALID, "mk_observation_weights: d_targets and d_weights are required");
     if (req->n_targets < 1) return fail(MK_ERR_INVALID, "mk_observation_weights: need n_targets >= 1 (got %lld)", (long long)req->n_targets);
     if (req->what != MK_DRAW_SERIES && req->what != MK_DRAW_STATES)
         return fail(MK_ERR_INVALID, "mk_observation_weights: what must be MK_DRAW_SERIES or MK_DRAW_STATES (got %d)", req->what);
     if (!p->d_obs || !p->d_loadings) return fail(MK_ERR_INVALID, "d_obs and d_loadings are required");
-    const int64_t ws = mk_weights_work_stride(p->N, p->K);
-    if (!ws) return too_many_states("mk_observation_weights", p, mk::weights_max_states);
-    const int64_t B = p->n_instances, M = req->n_targets, n = p->N + p->K;
-    const int64_t rs = mk::record_stride((int)n), gs = mk::weights_slot_stride(n);
+    if (!mk_weights_work_stride(p->N, p->K)) return too_many_states("mk_observation_weights", p, mk::weights_max_states);
+    const int64_t B = p->n_instances, M = req->n_targets;
+    const work_layout w = layout_of(WORK_GAIN, p->N, p->K, B, p->T);
     static_assert(sizeof(int64_t) == sizeof(double), "buffers_fit counts 8-byte words");
-    const device_buffer bufs[4] = {{d_work, B * p->T * ws, "d_work (n_instances * T * mk_weights_work_stride(N, K) doubles)"},
+    const device_buffer bufs[4] = {{d_work, B * p->T * w.stride, "d_work (n_instances * T * mk_weights_work_stride(N, K) doubles)"},
                                    {req->d_targets, p->n_records * M * 2, "d_targets (n_records * n_targets * 2 64-bit integers)"},
                                    {req->d_weights, B * M * p->T * p->N, "d_weights (n_instances * n_targets * T * N doubles)"},
                                    {req->d_intercept, B * M, "d_intercept (n_instances * n_targets doubles)"}};
     if (int rc = buffers_fit("mk_observation_weights", bufs, 4)) return rc;
-    // the records are packed at the head of d_work; the gain tape lives behind them
-    if (int rc = record_pass(ctx, p, d_work, rs, time_major, d_status)) return rc;
-    double *tape = d_work + B * p->T * rs;
-    mk::InnovArgs g;
-    memset(&g, 0, sizeof(g));
-    fill_model(g, p);
-    fill_initial(g, p);
-    fill_layout(g, time_major, B, p->T);
-    g.N = (int)p->N;
-    g.K = (int)p->K;
-    g.rs = rs;
-    g.F = d_work;
-    g.gain = tape;
-    g.gs = gs;
-    mk::WeightsArgs a;
-    memset(&a, 0, sizeof(a));
-    fill_model(a, p);
-    fill_initial(a, p);
-    fill_layout(a, time_major, B, p->T);
-    a.N = (int)p->N;
-    a.K = (int)p->K;
+    if (int rc = record_pass(ctx, p, d_work, w.rs, time_major, d_status)) return rc;
+    mk::WeightsArgs a = reader_args<mk::WeightsArgs>(p, d_work, w.rs, time_major);
     a.M = M;
     a.states = req->what == MK_DRAW_STATES ? 1 : 0;
-    a.rs = rs;
-    a.gs = gs;
-    a.F = d_work;
-    a.gain = tape;
+    a.gs = w.gs;
+    a.gain = d_work + w.tape;
     a.targets = req->d_targets;
     a.weights = req->d_weights;
     a.intercept = req->d_intercept;
-    MK_HIP(timing_start(ctx, 1));
-    // a cell that is not observed keeps an all-zero slot: innov_step_kernel writes the observed ones only
-    MK_HIP(hipMemsetAsync(tape, 0, sizeof(double) * (size_t)(B * p->T * p->N * gs), ctx->stream));
-    MK_HIP(mk::launch_innov_step(g, ctx->stream));
-    MK_HIP(mk::launch_weights_walk(a, ctx->stream));
-    MK_HIP(timing_stop(ctx, 1)); // reported in the smoother slot of mk_last_kernel_ms / mk_kernel_ms_totals
-    return MK_OK;
+    return timed_launches(ctx, [&]() -> int {
+        if (int rc = gain_tape_stage(ctx, p, d_work, w, time_major)) return rc;
+        MK_HIP(mk::launch_weights_walk(a, ctx->stream));
+        return MK_OK;
+    });
 }
 
 // ---- intervention effects by GLS (regress_kernels.hip) ----
@@ -1713,24 +1747,18 @@ static int check_effects(mk_context *ctx, const char *who, const int64_t *d_effe
 MK_API int mk_regression(mk_context *ctx, const mk_problem *p, double *d_work, int time_major, const mk_regression_request *req,
                          uint32_t *d_status)
 {
-    MK_CTX(ctx);
-    // refused first: every other shape that mk_regression_work_stride does not serve is one check_problem refuses
-    if (p && p->N >= 1 && p->K >= 1 && p->N + p->K > mk::regress_max_states) return too_many_states("mk_regression", p, mk::regress_max_states);
-    if (int rc = check_problem(p)) return rc;
-    if (!req) return fail(MK_ERR_INVALID, "mk_regression: null mk_regression_request");
-    if (!d_work) return fail(MK_ERR_INVALID, "mk_regression: d_work is required");
+    if (int rc = reader_preamble(ctx, "mk_regression", "mk_regression_request", p, mk::regress_max_states, req, d_work)) return rc;
     if (!req->d_effects || !req->d_beta || !req->d_cov || !req->d_gain || !req->d_normal || !req->d_support || !req->d_dropped)
         return fail(MK_ERR_INVALID, "mk_regression: d_effects, d_beta, d_cov, d_gain, d_normal, d_support and d_dropped are required");
     if (req->n_effects < 1 || req->n_effects > mk::regress_max_effects)
         return fail(MK_ERR_INVALID, "mk_regression: need 1 <= n_effects <= %d (got %lld)", mk::regress_max_effects, (long long)req->n_effects);
     if (req->t_first < 0) return fail(MK_ERR_INVALID, "mk_regression: t_first must be >= 0");
     if (!p->d_obs || !p->d_loadings) return fail(MK_ERR_INVALID, "d_obs and d_loadings are required");
-    const int64_t ws = mk_regression_work_stride(p->N, p->K);
-    if (!ws) return too_many_states("mk_regression", p, mk::regress_max_states);
-    const int64_t B = p->n_instances, M = req->n_effects, n = p->N + p->K;
-    const int64_t rs = mk::record_stride((int)n), gs = mk::weights_slot_stride(n);
+    if (!mk_regression_work_stride(p->N, p->K)) return too_many_states("mk_regression", p, mk::regress_max_states);
+    const int64_t B = p->n_instances, M = req->n_effects;
+    const work_layout w = layout_of(WORK_GAIN, p->N, p->K, B, p->T);
     static_assert(sizeof(int64_t) == sizeof(double), "buffers_fit counts 8-byte words");
-    const device_buffer bufs[8] = {{d_work, B * p->T * ws, "d_work (n_instances * T * mk_regression_work_stride(N, K) doubles)"},
+    const device_buffer bufs[8] = {{d_work, B * p->T * w.stride, "d_work (n_instances * T * mk_regression_work_stride(N, K) doubles)"},
                                    {req->d_effects, p->n_records * M * 4, "d_effects (n_records * n_effects * 4 64-bit integers)"},
                                    {req->d_beta, B * M, "d_beta (n_instances * n_effects doubles)"},
                                    {req->d_cov, B * M * M, "d_cov (n_instances * n_effects^2 doubles)"},
@@ -1740,31 +1768,12 @@ MK_API int mk_regression(mk_context *ctx, const mk_problem *p, double *d_work, i
                                    {req->d_dropped, (B + 1) / 2, "d_dropped (n_instances 32-bit words)"}};
     if (int rc = buffers_fit("mk_regression", bufs, 8)) return rc;
     if (int rc = check_effects(ctx, "mk_regression", req->d_effects, p->n_records, M, p->T, p->N)) return rc;
-    // the records are packed at the head of d_work; the gain tape lives behind them
-    if (int rc = record_pass(ctx, p, d_work, rs, time_major, d_status)) return rc;
-    double *tape = d_work + B * p->T * rs;
-    mk::InnovArgs g;
-    memset(&g, 0, sizeof(g));
-    fill_model(g, p);
-    fill_initial(g, p);
-    fill_layout(g, time_major, B, p->T);
-    g.N = (int)p->N;
-    g.K = (int)p->K;
-    g.rs = rs;
-    g.F = d_work;
-    g.gain = tape;
-    g.gs = gs;
-    mk::RegressArgs a;
-    memset(&a, 0, sizeof(a));
-    fill_model(a, p);
-    fill_initial(a, p);
-    fill_layout(a, time_major, B, p->T);
-    a.N = (int)p->N;
-    a.K = (int)p->K;
+    if (int rc = record_pass(ctx, p, d_work, w.rs, time_major, d_status)) return rc;
+    mk::RegressArgs a = reader_args<mk::RegressArgs>(p, d_work, w.rs, time_major); // the replay reads the tape, not the records
     a.M = M;
     a.t_first = req->t_first;
-    a.gs = gs;
-    a.gain = tape;
+    a.gs = w.gs;
+    a.gain = d_work + w.tape;
     a.effects = req->d_effects;
     a.beta = req->d_beta;
     a.cov = req->d_cov;
@@ -1772,13 +1781,11 @@ MK_API int mk_regression(mk_context *ctx, const mk_problem *p, double *d_work, i
     a.normal = req->d_normal;
     a.support = req->d_support;
     a.dropped = req->d_dropped;
-    MK_HIP(timing_start(ctx, 1));
-    // a cell that is not observed keeps an all-zero slot: innov_step_kernel writes the observed ones only
-    MK_HIP(hipMemsetAsync(tape, 0, sizeof(double) * (size_t)(B * p->T * p->N * gs), ctx->stream));
-    MK_HIP(mk::launch_innov_step(g, ctx->stream));
-    MK_HIP(mk::launch_regress_replay(a, ctx->stream));
-    MK_HIP(timing_stop(ctx, 1)); // reported in the smoother slot of mk_last_kernel_ms / mk_kernel_ms_totals
-    return MK_OK;
+    return timed_launches(ctx, [&]() -> int {
+        if (int rc = gain_tape_stage(ctx, p, d_work, w, time_major)) return rc;
+        MK_HIP(mk::launch_regress_replay(a, ctx->stream));
+        return MK_OK;
+    });
 }
 
 MK_API int mk_regression_adjust(mk_context *ctx, int64_t R, int64_t T, int64_t N, int time_major, int64_t n_effects,
@@ -1818,28 +1825,21 @@ MK_API int64_t mk_scores_max_states(void) { return mk::score_max_states; }
 MK_API int64_t mk_scores_work_stride(int64_t N, int64_t K)
 {
     static_assert(mk::score_max_states == mk::weights_max_states, "the scores run on the weights' workspace and a row of innovations");
-    const int64_t ws = mk_weights_work_stride(N, K);
-    return ws ? ws + N : 0;
+    return mk_weights_work_stride(N, K) ? layout_of(WORK_SCORES, N, K).stride : 0;
 }
 
 MK_API int mk_scores(mk_context *ctx, const mk_problem *p, double *d_work, int time_major, const mk_scores_request *req, uint32_t *d_status)
 {
-    MK_CTX(ctx);
-    // refused first: every other shape that mk_scores_work_stride does not serve is one check_problem refuses
-    if (p && p->N >= 1 && p->K >= 1 && p->N + p->K > mk::score_max_states) return too_many_states("mk_scores", p, mk::score_max_states);
-    if (int rc = check_problem(p)) return rc;
-    if (!req) return fail(MK_ERR_INVALID, "mk_scores: null mk_scores_request");
-    if (!d_work) return fail(MK_ERR_INVALID, "mk_scores: d_work is required");
+    if (int rc = reader_preamble(ctx, "mk_scores", "mk_scores_request", p, mk::score_max_states, req, d_work)) return rc;
     if (!req->d_dphi || !req->d_dq || !req->d_score || !req->d_grad || !req->d_count || !req->d_opg || !req->d_cusum)
         return fail(MK_ERR_INVALID, "mk_scores: d_dphi, d_dq, d_score, d_grad, d_count, d_opg and d_cusum are required");
     if (req->t_first < 0) return fail(MK_ERR_INVALID, "mk_scores: t_first must be >= 0");
     if (!p->d_obs || !p->d_loadings) return fail(MK_ERR_INVALID, "d_obs and d_loadings are required");
-    const int64_t ws = mk_scores_work_stride(p->N, p->K);
-    if (!ws) return too_many_states("mk_scores", p, mk::score_max_states);
+    if (!mk_scores_work_stride(p->N, p->K)) return too_many_states("mk_scores", p, mk::score_max_states);
     const int64_t B = p->n_instances, n = p->N + p->K;
-    const int64_t rs = mk::record_stride((int)n), gs = mk::weights_slot_stride(n);
+    const work_layout w = layout_of(WORK_SCORES, p->N, p->K, B, p->T);
     static_assert(sizeof(int64_t) == sizeof(double), "buffers_fit counts 8-byte words");
-    const device_buffer bufs[8] = {{d_work, B * p->T * ws, "d_work (n_instances * T * mk_scores_work_stride(N, K) doubles)"},
+    const device_buffer bufs[8] = {{d_work, B * p->T * w.stride, "d_work (n_instances * T * mk_scores_work_stride(N, K) doubles)"},
                                    {req->d_dphi, B * n, "d_dphi (n_instances * (N + K) doubles)"},
                                    {req->d_dq, B * n, "d_dq (n_instances * (N + K) doubles)"},
                                    {req->d_score, B * p->T * n, "d_score (n_instances * T * (N + K) doubles)"},
@@ -1848,35 +1848,12 @@ MK_API int mk_scores(mk_context *ctx, const mk_problem *p, double *d_work, int t
                                    {req->d_opg, B * n * n, "d_opg (n_instances * (N + K)^2 doubles)"},
                                    {req->d_cusum, B * n * n, "d_cusum (n_instances * (N + K)^2 doubles)"}};
     if (int rc = buffers_fit("mk_scores", bufs, 8)) return rc;
-    // the records are packed at the head of d_work; the gain tape lives behind them, the innovations behind the tape
-    if (int rc = record_pass(ctx, p, d_work, rs, time_major, d_status)) return rc;
-    double *tape = d_work + B * p->T * rs;
-    double *innov = tape + B * p->T * p->N * gs;
-    mk::InnovArgs g;
-    memset(&g, 0, sizeof(g));
-    fill_model(g, p);
-    fill_initial(g, p);
-    fill_layout(g, time_major, B, p->T);
-    g.N = (int)p->N;
-    g.K = (int)p->K;
-    g.rs = rs;
-    g.F = d_work;
-    g.v = innov;
-    g.gain = tape;
-    g.gs = gs;
-    mk::ScoreArgs a;
-    memset(&a, 0, sizeof(a));
-    fill_model(a, p);
-    fill_initial(a, p);
-    fill_layout(a, time_major, B, p->T);
-    a.N = (int)p->N;
-    a.K = (int)p->K;
+    if (int rc = record_pass(ctx, p, d_work, w.rs, time_major, d_status)) return rc;
+    mk::ScoreArgs a = reader_args<mk::ScoreArgs>(p, d_work, w.rs, time_major);
     a.t_first = req->t_first;
-    a.rs = rs;
-    a.gs = gs;
-    a.F = d_work;
-    a.gain = tape;
-    a.v = innov;
+    a.gs = w.gs;
+    a.gain = d_work + w.tape;
+    a.v = d_work + w.innov;
     a.dphi = req->d_dphi;
     a.dq = req->d_dq;
     a.score = req->d_score;
@@ -1884,14 +1861,12 @@ MK_API int mk_scores(mk_context *ctx, const mk_problem *p, double *d_work, int t
     a.count = req->d_count;
     a.opg = req->d_opg;
     a.cusum = req->d_cusum;
-    MK_HIP(timing_start(ctx, 1));
-    // a cell that is not observed keeps an all-zero slot: innov_step_kernel writes the observed ones only
-    MK_HIP(hipMemsetAsync(tape, 0, sizeof(double) * (size_t)(B * p->T * p->N * gs), ctx->stream));
-    MK_HIP(mk::launch_innov_step(g, ctx->stream));
-    MK_HIP(mk::launch_score_tangent(a, ctx->stream));
-    MK_HIP(mk::launch_score_stats(a, ctx->stream));
-    MK_HIP(timing_stop(ctx, 1)); // reported in the smoother slot of mk_last_kernel_ms / mk_kernel_ms_totals
-    return MK_OK;
+    return timed_launches(ctx, [&]() -> int {
+        if (int rc = gain_tape_stage(ctx, p, d_work, w, time_major, d_work + w.innov)) return rc;
+        MK_HIP(mk::launch_score_tangent(a, ctx->stream));
+        MK_HIP(mk::launch_score_stats(a, ctx->stream));
+        return MK_OK;
+    });
 }
 
 // ---- exact window means, changes and contrasts of the smoothed signal (functional_kernels.hip) ----
@@ -1900,19 +1875,13 @@ MK_API int64_t mk_functionals_max_contrasts(void) { return mk::functional_max_co
 MK_API int64_t mk_functionals_work_stride(int64_t N, int64_t K)
 {
     if (N < 1 || K < 1 || N + K > mk::functional_max_states || !mk_shape_supported(N, K)) return 0;
-    return 2 * (int64_t)mk::record_stride((int)(N + K)); // the filtered and the smoothed record of a step
+    return layout_of(WORK_FUNCTIONALS, N, K).stride; // the filtered and the smoothed record of a step
 }
 
 MK_API int mk_functionals(mk_context *ctx, const mk_problem *p, double *d_work, int time_major, const mk_functional_request *req,
                           double *d_mean, double *d_var, uint32_t *d_status)
 {
-    MK_CTX(ctx);
-    // refused first: every other shape that mk_functionals_work_stride does not serve is one check_problem refuses
-    if (p && p->N >= 1 && p->K >= 1 && p->N + p->K > mk::functional_max_states)
-        return too_many_states("mk_functionals", p, mk::functional_max_states);
-    if (int rc = check_problem(p)) return rc;
-    if (!req) return fail(MK_ERR_INVALID, "mk_functionals: null mk_functional_request");
-    if (!d_work) return fail(MK_ERR_INVALID, "mk_functionals: d_work is required");
+    if (int rc = reader_preamble(ctx, "mk_functionals", "mk_functional_request", p, mk::functional_max_states, req, d_work)) return rc;
     if (!req->d_windows || !d_mean || !d_var) return fail(MK_ERR_INVALID, "mk_functionals: d_windows, d_mean and d_var are required");
     if (req->n_windows < 1) return fail(MK_ERR_INVALID, "mk_functionals: need n_windows >= 1 (got %lld)", (long long)req->n_windows);
     if (req->n_contrasts < 1 || req->n_contrasts > mk::functional_max_contrasts)
@@ -1922,21 +1891,19 @@ MK_API int mk_functionals(mk_context *ctx, const mk_problem *p, double *d_work, 
         return fail(MK_ERR_INVALID, "mk_functionals: d_contrasts = NULL stands for the N unit contrasts, n_contrasts must be N = %lld (got %lld)",
                     (long long)p->N, (long long)req->n_contrasts);
     if (!p->d_obs || !p->d_loadings) return fail(MK_ERR_INVALID, "d_obs and d_loadings are required");
-    const int64_t ws = mk_functionals_work_stride(p->N, p->K);
-    if (!ws) return too_many_states("mk_functionals", p, mk::functional_max_states);
+    if (!mk_functionals_work_stride(p->N, p->K)) return too_many_states("mk_functionals", p, mk::functional_max_states);
     const int64_t B = p->n_instances, W = req->n_windows, C = req->n_contrasts, n = p->N + p->K;
-    const int64_t rs = mk::record_stride((int)n);
+    const work_layout w = layout_of(WORK_FUNCTIONALS, p->N, p->K, B, p->T);
     static_assert(sizeof(int64_t) == sizeof(double), "buffers_fit counts 8-byte words");
-    const device_buffer bufs[5] = {{d_work, B * p->T * ws, "d_work (n_instances * T * mk_functionals_work_stride(N, K) doubles)"},
+    const device_buffer bufs[5] = {{d_work, B * p->T * w.stride, "d_work (n_instances * T * mk_functionals_work_stride(N, K) doubles)"},
                                    {req->d_windows, p->n_records * W * 4, "d_windows (n_records * n_windows * 4 64-bit integers)"},
                                    {req->d_contrasts, p->n_records * C * p->N, "d_contrasts (n_records * n_contrasts * N doubles)"},
                                    {d_mean, B * W * C, "d_mean (n_instances * n_windows * n_contrasts doubles)"},
                                    {d_var, B * W * C, "d_var (n_instances * n_windows * n_contrasts doubles)"}};
     if (int rc = buffers_fit("mk_functionals", bufs, 5)) return rc;
-    // the filtered records are packed at the head of d_work, the smoothed ones behind them: the forward pass and the smoother of
-    // mk_filter_smooth for the shape (full-square records, no projection), then the walk
-    if (int rc = record_pass(ctx, p, d_work, rs, time_major, d_status)) return rc;
-    double *smoothed = d_work + B * p->T * rs;
+    // the forward pass and the smoother of mk_filter_smooth for the shape (full-square records, no projection), then the walk
+    if (int rc = record_pass(ctx, p, d_work, w.rs, time_major, d_status)) return rc;
+    double *smoothed = d_work + w.smoothed;
     mk_outputs o;
     memset(&o, 0, sizeof(o));
     o.d_status = d_status;
@@ -1945,7 +1912,7 @@ MK_API int mk_functionals(mk_context *ctx, const mk_problem *p, double *d_work, 
     o.d_S = smoothed;
     o.d_Ps = smoothed + n;
     o.time_major = time_major;
-    o.record_stride = rs;
+    o.record_stride = w.rs;
     if (int rc = do_smooth(ctx, p, &o, false)) return rc;
     mk::FunctionalArgs a;
     memset(&a, 0, sizeof(a));
@@ -1958,7 +1925,7 @@ MK_API int mk_functionals(mk_context *ctx, const mk_problem *p, double *d_work, 
     a.K = (int)p->K;
     fill_layout(a, time_major, B, p->T);
     fill_scaling(a, p);
-    a.rs = rs;
+    a.rs = w.rs;
     a.phi = p->d_phi;
     a.q = p->d_q;
     a.loadings = p->d_loadings;
@@ -1969,10 +1936,10 @@ MK_API int mk_functionals(mk_context *ctx, const mk_problem *p, double *d_work, 
     a.mean = d_mean;
     a.var = d_var;
     a.status = d_status;
-    MK_HIP(timing_start(ctx, 1));
-    MK_HIP(mk::launch_functional_walk(a, ctx->stream));
-    MK_HIP(timing_stop(ctx, 1)); // reported in the smoother slot of mk_last_kernel_ms / mk_kernel_ms_totals, beside the smoother's own launch
-    return MK_OK;
+    return timed_launches(ctx, [&]() -> int {
+        MK_HIP(mk::launch_functional_walk(a, ctx->stream));
+        return MK_OK;
+    });
 }
 
 // ---- lock-step L-BFGS of the batched calibration (mk_lbfgs.hip) ----

@@ -709,62 +709,102 @@ class BatchedKalman:
         return res
 
     # ------------------------------------------------------------------ the record readers: one scaffold
-    # loo_predict, disturbances, innovations, forecast, observation_weights, regression, scores and functionals (which also runs the smoother) run the recording forward pass into a workspace ("_work") and one kernel
-    # that reads its filtered records.  NOTE: loo_supported() and disturbances_supported() are methods, innovations_supported and
-    # forecast_supported / observation_weights_supported / regression_supported / scores_supported / functionals_supported properties -- an inconsistency of the public API that is kept.
-    def _reader_stride(self, fn, specialised_only, refusal=None):
-        """Doubles per (instance, step) of a record reader's workspace, the C ABI's ``fn(N, K)``; where the shape is not served
-        0, or with ``refusal`` (a text with places for N and K) a MetranHipError."""
+    # loo_predict, disturbances, innovations, forecast, observation_weights, regression, scores and functionals (which also runs
+    # the smoother) run the recording forward pass into a workspace ("_work") and kernels that read its filtered records.  What a
+    # reader keeps to itself is the validation of its request, its shapes and its request struct; the table, _reader_stride,
+    # _reader_shapes, _reader_buffers and _reader_call are the rest.
+    # reader -> (stride function of the C ABI, specialised kernels only, who reads full-square records only (None: packed-symmetric
+    # engines are served too), what the refusal of a shape says is served, allocator)
+    _READERS = {
+        "loo": ("mk_loo_work_stride", True, None, "leave-one-out predictions serve specialised shapes with N + K <= 63", "alloc_loo"),
+        "disturbances": ("mk_disturbance_work_stride", True, None, "state disturbances serve specialised shapes with N + K <= 64",
+                         "alloc_disturbances"),
+        "innovations": ("mk_innovations_work_stride", False, None, "innovations serve shapes with N + K <= 64", "alloc_innovations"),
+        "forecast": ("mk_forecast_work_stride", False, None, "forecasts serve shapes with N + K <= 64", "alloc_forecast"),
+        "weights": ("mk_weights_work_stride", False, None, "observation weights serve shapes with N + K <= 64",
+                    "alloc_observation_weights"),
+        "regression": ("mk_regression_work_stride", False, None, "intervention effects serve shapes with N + K <= 64", "alloc_regression"),
+        "scores": ("mk_scores_work_stride", False, "the scores", "per-step scores serve shapes with N + K <= 64", "alloc_scores"),
+        "functionals": ("mk_functionals_work_stride", False, "window functionals", "window functionals serve shapes with N + K <= 64",
+                        "alloc_functionals"),
+    }
+
+    # NOTE: loo_supported() and disturbances_supported() are methods, innovations_supported, forecast_supported,
+    # observation_weights_supported, regression_supported, scores_supported and functionals_supported properties -- an
+    # inconsistency of the public API that is kept.
+    def _reader_stride(self, name, refuse=False):
+        """Doubles per (instance, step) of the workspace of the record reader ``name``; where the engine is not served 0, or with
+        ``refuse`` a MetranHipError."""
+        fn, specialised_only, full_square, serves, _ = self._READERS[name]
+        if full_square and self.packed_sym:
+            if refuse:
+                raise MetranHipError("libmetran_hip error -2 (MK_ERR_SHAPE): %s read full-square records; this engine was "
+                                     "created with packed_sym=True" % full_square)
+            return 0
         served = self.loadings is not None and (not specialised_only or self.get_variant("kernel_family") == "specialised")
-        stride = int(fn(self.N, self.K)) if served else 0
-        if not stride and refusal is not None:
-            raise MetranHipError(refusal % (self.N, getattr(self, "K", None)))
+        stride = int(getattr(self._L, fn)(self.N, self.K)) if served else 0
+        if not stride and refuse:
+            raise MetranHipError("%s; (N=%s, K=%s) is not one" % (serves, self.N, getattr(self, "K", None)))
         return stride
 
-    def _bt_shapes(self, B, **tails):
-        """name -> (logical shape, follows the engine's layout) of ``[B,T,tail]`` buffers."""
-        return {key: ((B, self.T, tail), True) for key, tail in tails.items()}
-
-    def _reader_buffers(self, buffers, shapes, alloc, sep=","):
-        """The buffers of a record reader, ``shapes`` being name -> (logical shape, follows the engine's layout): allocated with a
-        zeroed ``status``, or the caller's ``buffers`` -- checked either way.  ``alloc`` names the allocator in the refusal."""
+    def _reader_shapes(self, B, bt=None, ints=None, **plain):
+        """name -> (logical shape, follows the engine's layout, dtype) of a record reader's outputs: the float64 ``[B,T,tail]``
+        buffers ``bt`` (key -> tail), the contiguous float64 buffers ``plain`` (key -> shape), the contiguous integer buffers
+        ``ints`` (key -> (shape, dtype)) and ``status``."""
         torch = _torch()
-        res = buffers
-        if res is None:
-            res = {key: self._empty_bt(*shape) if bt else torch.empty(shape, dtype=torch.float64, device=self.device)
-                   for key, (shape, bt) in shapes.items()}
-            res["status"] = torch.zeros(shapes["_work"][0][0], dtype=torch.int32, device=self.device)
-        for key, (shape, bt) in shapes.items():
-            t = res.get(key)
-            if t is None or tuple(t.shape) != shape or not ((self._layout(t) is t) if bt else t.is_contiguous()):
-                raise ValueError("buffers[%r] must be a [%s] tensor%s (%s)" % (key, sep.join("%d" % d for d in shape),
-                                                                              " in the engine's layout" if bt else "", alloc))
-        return res
+        shapes = {key: ((B, self.T, tail), True, torch.float64) for key, tail in (bt or {}).items()}
+        for key, shape in plain.items():
+            shapes[key] = (shape, False, torch.float64)
+        for key, (shape, dtype) in (ints or {}).items():
+            shapes[key] = (shape, False, dtype)
+        shapes["status"] = ((B,), False, torch.int32)
+        return shapes
 
-    @staticmethod
-    def _mask_bad_instances(res, keys):
-        """NaN in every row of the instances whose status carries ``FLAG_NONPOSITIVE_F``."""
-        bad = (res["status"] & FLAG_NONPOSITIVE_F) != 0
-        for key in keys:
-            res[key].masked_fill_(bad.view((-1,) + (1,) * (res[key].ndim - 1)), float("nan"))
+    def _reader_buffers(self, name, buffers, shapes, stride=None):
+        """The buffers of the record reader ``name``: its workspace of ``stride`` doubles per (instance, step) (None: asked for
+        here) and what ``shapes`` lists (``_reader_shapes``; the workspace is added to it) -- allocated with a zeroed ``status``,
+        or the caller's ``buffers``, every one of them checked before anything is bound or launched."""
+        torch = _torch()
+        B = shapes["status"][0][0]
+        shapes["_work"] = ((B, self.T, stride or self._reader_stride(name, refuse=True)), True, torch.float64)
+        if buffers is None:
+            return {key: self._empty_bt(*shape, dtype=dtype) if bt else
+                    (torch.zeros if key == "status" else torch.empty)(shape, dtype=dtype, device=self.device)
+                    for key, (shape, bt, dtype) in shapes.items()}
+        for key, (shape, bt, dtype) in shapes.items():
+            t = buffers.get(key)
+            if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.device == self.device and t.shape == shape
+                    and (t.transpose(0, 1) if bt and self.time_major else t).is_contiguous()):
+                raise ValueError("buffers[%r] must be a %s [%s] tensor on %s%s (%s)" % (
+                    key, str(dtype).replace("torch.", ""), ", ".join("%d" % d for d in shape), self.device,
+                    " in the engine's layout" if bt else ", contiguous", self._READERS[name][-1]))
+        return buffers
+
+    def _reader_call(self, entry, prob, res, *specific, mask=()):
+        """The tail of every record reader: the C ABI's ``entry(ctx, prob, work, time_major, *specific, status)`` on the current
+        stream, then NaN in every row of ``mask`` of the instances whose status carries ``FLAG_NONPOSITIVE_F``."""
+        self._bind_stream()
+        check(getattr(self._L, entry)(self._ctx, ctypes.byref(prob), self._p(res["_work"]), 1 if self.time_major else 0, *specific,
+                                      self._p(res["status"])))
+        if mask:
+            bad = (res["status"] & FLAG_NONPOSITIVE_F) != 0
+            for key in mask:
+                res[key].masked_fill_(bad.view((-1,) + (1,) * (res[key].ndim - 1)), float("nan"))
+        return res
 
     # ------------------------------------------------------------------ leave-one-out predictions
     def loo_supported(self):
         """True when ``loo_predict`` serves this engine's shape (C ABI ``mk_loo_work_stride`` > 0): specialised kernels and
         N + K <= 63 -- the adjoint walk over filtered records for N + K <= 16, the tape walk above."""
-        return self._reader_stride(self._L.mk_loo_work_stride, True) > 0
-
-    def _loo_stride(self):
-        return self._reader_stride(self._L.mk_loo_work_stride, True,
-                                   "leave-one-out predictions serve specialised shapes with N + K <= 63; (N=%s, K=%s) is not one")
+        return self._reader_stride("loo") > 0
 
     def _loo_shapes(self, B):
-        return self._bt_shapes(B, _work=self._loo_stride(), loo_means=self.N, loo_vars=self.N)
+        return self._reader_shapes(B, bt=dict(loo_means=self.N, loo_vars=self.N))
 
     def alloc_loo(self, B):
         """Buffers of ``loo_predict`` for B instances (the forward pass's workspace + the two outputs), for callers that run
         it repeatedly (pass them back as ``buffers=``)."""
-        return self._reader_buffers(None, self._loo_shapes(B), "alloc_loo")
+        return self._reader_buffers("loo", None, self._loo_shapes(B))
 
     def loo_predict(self, phi, q, x0=None, P0=None, buffers=None):
         """LEAVE-ONE-OUT predictions of every observed cell for B instances (C ABI ``mk_loo``): ``loo_means[b,t,j]`` is the
@@ -773,31 +813,24 @@ class BatchedKalman:
         cell gives (Metran's outlier screen, metran.py:464-506 + 831-883), parameters held fixed -- for all cells in two
         launches.  Units as set by ``set_scaling`` (scale / offset of the projection); NaN where a cell is not observed.
         Returns a dict with ``loo_means, loo_vars`` ``[B,T,N]`` and ``status`` (the filter's MK_FLAG_* bits)."""
-        self._loo_stride()
+        stride = self._reader_stride("loo", refuse=True)
         prob, keep, B = self._problem(phi, q, 0, x0, P0)
-        res = self._reader_buffers(buffers, self._loo_shapes(B), "alloc_loo")
-        self._bind_stream()
-        check(self._L.mk_loo(self._ctx, ctypes.byref(prob), self._p(res["_work"]), 1 if self.time_major else 0,
-                             self._p(res["loo_means"]), self._p(res["loo_vars"]), self._p(res["status"])))
-        return res
+        res = self._reader_buffers("loo", buffers, self._loo_shapes(B), stride)
+        return self._reader_call("mk_loo", prob, res, self._p(res["loo_means"]), self._p(res["loo_vars"]))
 
     # ------------------------------------------------------------------ smoothed state disturbances
     def disturbances_supported(self):
         """True when ``disturbances`` serves this engine's shape (C ABI ``mk_disturbance_work_stride`` > 0): specialised
         kernels and N + K <= 64 -- ``adjoint_kernel`` for N + K <= 16, ``adjoint_wide_kernel`` above, in their disturbance mode."""
-        return self._reader_stride(self._L.mk_disturbance_work_stride, True) > 0
-
-    def _disturbance_stride(self):
-        return self._reader_stride(self._L.mk_disturbance_work_stride, True,
-                                   "state disturbances serve specialised shapes with N + K <= 64; (N=%s, K=%s) is not one")
+        return self._reader_stride("disturbances") > 0
 
     def _disturbance_shapes(self, B):
-        return self._bt_shapes(B, _work=self._disturbance_stride(), r=self.n, ninfo=self.n)
+        return self._reader_shapes(B, bt=dict(r=self.n, ninfo=self.n))
 
     def alloc_disturbances(self, B):
         """Buffers of ``disturbances`` for B instances (the forward pass's workspace + the two outputs), for callers that run
         it repeatedly (pass them back as ``buffers=``)."""
-        return self._reader_buffers(None, self._disturbance_shapes(B), "alloc_disturbances")
+        return self._reader_buffers("disturbances", None, self._disturbance_shapes(B))
 
     def disturbances(self, phi, q, x0=None, P0=None, buffers=None):
         """Smoothed STATE DISTURBANCES for B instances (C ABI ``mk_disturbances``): the Durbin-Koopman backward pair of the
@@ -807,13 +840,10 @@ class BatchedKalman:
         Koopman 1992; unit spread under the model, large where the state equation failed).  The raw pair is returned so that
         ``u`` is never formed from a difference.  Two launches: the recording forward pass and one backward walk.
         Returns a dict with ``r, ninfo`` ``[B,T,n]`` and ``status`` (the filter's MK_FLAG_* bits)."""
-        self._disturbance_stride()
+        stride = self._reader_stride("disturbances", refuse=True)
         prob, keep, B = self._problem(phi, q, 0, x0, P0)
-        res = self._reader_buffers(buffers, self._disturbance_shapes(B), "alloc_disturbances")
-        self._bind_stream()
-        check(self._L.mk_disturbances(self._ctx, ctypes.byref(prob), self._p(res["_work"]), 1 if self.time_major else 0,
-                                      self._p(res["r"]), self._p(res["ninfo"]), self._p(res["status"])))
-        return res
+        res = self._reader_buffers("disturbances", buffers, self._disturbance_shapes(B), stride)
+        return self._reader_call("mk_disturbances", prob, res, self._p(res["r"]), self._p(res["ninfo"]))
 
     # ------------------------------------------------------------------ one-step-ahead innovations
     _INNOVATION_OUTPUTS = ("v", "f", "pred_mean", "pred_var")
@@ -822,19 +852,15 @@ class BatchedKalman:
     def innovations_supported(self):
         """True when ``innovations`` serves this engine's shape (C ABI ``mk_innovations_work_stride`` > 0): N + K <= 64,
         specialised or size-generic kernels alike."""
-        return self._reader_stride(self._L.mk_innovations_work_stride, False) > 0
-
-    def _innovations_stride(self):
-        return self._reader_stride(self._L.mk_innovations_work_stride, False,
-                                   "innovations serve shapes with N + K <= 64; (N=%s, K=%s) is not one")
+        return self._reader_stride("innovations") > 0
 
     def _innovations_shapes(self, B, outputs):
-        return self._bt_shapes(B, _work=self._innovations_stride(), **{key: self.N for key in outputs})
+        return self._reader_shapes(B, bt={key: self.N for key in outputs})
 
     def alloc_innovations(self, B, outputs=_INNOVATION_OUTPUTS):
         """Buffers of ``innovations`` for B instances (the forward pass's workspace + the outputs asked for), for callers that
         run it repeatedly (pass them back as ``buffers=``)."""
-        return self._reader_buffers(None, self._innovations_shapes(B, outputs), "alloc_innovations")
+        return self._reader_buffers("innovations", None, self._innovations_shapes(B, outputs))
 
     def innovations(self, phi, q, x0=None, P0=None, buffers=None, outputs=_INNOVATION_OUTPUTS):
         """ONE-STEP-AHEAD innovations for B instances (C ABI ``mk_innovations``): ``v[b,t,j]`` and ``f[b,t,j]`` are the innovation
@@ -847,15 +873,11 @@ class BatchedKalman:
         outputs = tuple(outputs)
         if not outputs or any(k not in self._INNOVATION_OUTPUTS for k in outputs):
             raise ValueError("outputs must be a non-empty subset of %s" % (self._INNOVATION_OUTPUTS,))
-        self._innovations_stride()
+        stride = self._reader_stride("innovations", refuse=True)
         prob, keep, B = self._problem(phi, q, 0, x0, P0)
-        res = self._reader_buffers(buffers, self._innovations_shapes(B, outputs), "alloc_innovations")
-        ptr = {k: self._p(res[k]) if k in outputs else None for k in self._INNOVATION_OUTPUTS}
-        self._bind_stream()
-        check(self._L.mk_innovations(self._ctx, ctypes.byref(prob), self._p(res["_work"]), 1 if self.time_major else 0,
-                                     ptr["v"], ptr["f"], ptr["pred_mean"], ptr["pred_var"], self._p(res["status"])))
-        self._mask_bad_instances(res, outputs)
-        return res
+        res = self._reader_buffers("innovations", buffers, self._innovations_shapes(B, outputs), stride)
+        ptr = [self._p(res[k]) if k in outputs else None for k in self._INNOVATION_OUTPUTS]
+        return self._reader_call("mk_innovations", prob, res, *ptr, mask=outputs)
 
     def innovation_stats(self, v, f, nlags=10, t_first=0):
         """Whiteness statistics of the standardised innovations ``e = v / sqrt(f)`` per (instance, series) (C ABI
@@ -889,22 +911,15 @@ class BatchedKalman:
     def forecast_supported(self):
         """True when ``forecast`` serves this engine's shape (C ABI ``mk_forecast_work_stride`` > 0): N + K <= 64,
         specialised or size-generic kernels alike."""
-        return self._reader_stride(self._L.mk_forecast_work_stride, False) > 0
-
-    def _forecast_stride(self):
-        return self._reader_stride(self._L.mk_forecast_work_stride, False,
-                                   "forecasts serve shapes with N + K <= 64; (N=%s, K=%s) is not one")
+        return self._reader_stride("forecast") > 0
 
     def _forecast_shapes(self, B, horizon, outputs):
-        """name -> (logical shape, follows the engine's layout) of the buffers of ``forecast``."""
-        shapes = self._bt_shapes(B, _work=self._forecast_stride())
+        plain = {}
         if "fan" in outputs:
-            shapes["fan_mean"] = shapes["fan_var"] = ((B, horizon, self.N), False)
-        if "track" in outputs:
-            shapes["track_mean"] = shapes["track_var"] = ((B, self.T, self.N), True)
+            plain["fan_mean"] = plain["fan_var"] = (B, horizon, self.N)
         if "skill" in outputs:
-            shapes["skill"] = ((B, self.N, horizon, 6), False)
-        return shapes
+            plain["skill"] = (B, self.N, horizon, 6)
+        return self._reader_shapes(B, bt=dict(track_mean=self.N, track_var=self.N) if "track" in outputs else None, **plain)
 
     def _forecast_request(self, horizon, outputs):
         outputs = tuple(outputs)
@@ -919,7 +934,7 @@ class BatchedKalman:
         """Buffers of ``forecast`` for B instances (the forward pass's workspace + the outputs asked for), for callers that run
         it repeatedly (pass them back as ``buffers=``)."""
         horizon, outputs = self._forecast_request(horizon, outputs)
-        return self._reader_buffers(None, self._forecast_shapes(B, horizon, outputs), "alloc_forecast", sep=", ")
+        return self._reader_buffers("forecast", None, self._forecast_shapes(B, horizon, outputs))
 
     def forecast(self, phi, q, x0=None, P0=None, horizon=14, outputs=("fan", "skill"), origins=None, track_horizon=1, t_first=1,
                  coverage=0.95, buffers=None):
@@ -949,10 +964,10 @@ class BatchedKalman:
             raise ValueError("t_first must be >= 0")
         if not 0.0 < coverage < 1.0:
             raise ValueError("coverage must be in (0, 1)")
-        self._forecast_stride()
+        stride = self._reader_stride("forecast", refuse=True)
         prob, keep, B = self._problem(phi, q, 0, x0, P0)
         shapes = self._forecast_shapes(B, horizon, outputs)
-        res = self._reader_buffers(buffers, shapes, "alloc_forecast", sep=", ")
+        res = self._reader_buffers("forecast", buffers, shapes, stride)
         org = None
         if origins is not None and "fan" in outputs:
             org = torch.as_tensor(origins, dtype=torch.int64).reshape(-1).to(self.device).contiguous()
@@ -965,29 +980,18 @@ class BatchedKalman:
         for field, key in (("d_fan_means", "fan_mean"), ("d_fan_vars", "fan_var"), ("d_track_means", "track_mean"),
                            ("d_track_vars", "track_var"), ("d_skill", "skill")):
             setattr(req, field, res[key].data_ptr() if key in shapes else None)
-        self._bind_stream()
-        check(self._L.mk_forecast(self._ctx, ctypes.byref(prob), self._p(res["_work"]), 1 if self.time_major else 0, ctypes.byref(req),
-                                  self._p(res["status"])))
-        self._mask_bad_instances(res, [key for key in shapes if key != "_work"])
-        return res
+        return self._reader_call("mk_forecast", prob, res, ctypes.byref(req),
+                                 mask=[key for key in shapes if key not in ("_work", "status")])
 
     # ------------------------------------------------------------------ observation weights of smoothed series and states
     @property
     def observation_weights_supported(self):
         """True when ``observation_weights`` serves this engine's shape (C ABI ``mk_weights_work_stride`` > 0): N + K <= 64,
         specialised or size-generic kernels alike."""
-        return self._reader_stride(self._L.mk_weights_work_stride, False) > 0
-
-    def _weights_stride(self):
-        return self._reader_stride(self._L.mk_weights_work_stride, False,
-                                   "observation weights serve shapes with N + K <= 64; (N=%s, K=%s) is not one")
+        return self._reader_stride("weights") > 0
 
     def _weights_shapes(self, B, M):
-        """name -> (logical shape, follows the engine's layout) of the buffers of ``observation_weights``."""
-        shapes = self._bt_shapes(B, _work=self._weights_stride())
-        shapes["weights"] = ((B, M, self.T, self.N), False)
-        shapes["intercept"] = ((B, M), False)
-        return shapes
+        return self._reader_shapes(B, weights=(B, M, self.T, self.N), intercept=(B, M))
 
     def alloc_observation_weights(self, B, M):
         """Buffers of ``observation_weights`` for B instances and M targets per record (the forward pass's workspace with the
@@ -995,7 +999,7 @@ class BatchedKalman:
         M = int(M)
         if M < 1:
             raise ValueError("M must be >= 1")
-        return self._reader_buffers(None, self._weights_shapes(B, M), "alloc_observation_weights", sep=", ")
+        return self._reader_buffers("weights", None, self._weights_shapes(B, M))
 
     def observation_weights(self, phi, q, targets, what="series", x0=None, P0=None, buffers=None):
         """OBSERVATION WEIGHTS of smoothed series or states for B instances (C ABI ``mk_observation_weights``; Koopman & Harvey
@@ -1011,7 +1015,7 @@ class BatchedKalman:
         torch = _torch()
         if what not in ("series", "states"):
             raise ValueError("what must be 'series' or 'states'")
-        self._weights_stride()
+        stride = self._reader_stride("weights", refuse=True)
         tg = torch.as_tensor(targets, dtype=torch.int64)
         if tg.ndim == 2:
             tg = tg[None].expand(self.R, -1, -1)
@@ -1020,15 +1024,11 @@ class BatchedKalman:
         tg = tg.to(self.device).contiguous()
         M = int(tg.shape[1])
         prob, keep, B = self._problem(phi, q, 0, x0, P0)
-        res = self._reader_buffers(buffers, self._weights_shapes(B, M), "alloc_observation_weights", sep=", ")
+        res = self._reader_buffers("weights", buffers, self._weights_shapes(B, M), stride)
         req = WeightsRequest()
         req.n_targets, req.what = M, 0 if what == "series" else 1   # MK_DRAW_SERIES / MK_DRAW_STATES
         req.d_targets, req.d_weights, req.d_intercept = tg.data_ptr(), res["weights"].data_ptr(), res["intercept"].data_ptr()
-        self._bind_stream()
-        check(self._L.mk_observation_weights(self._ctx, ctypes.byref(prob), self._p(res["_work"]), 1 if self.time_major else 0,
-                                             ctypes.byref(req), self._p(res["status"])))
-        self._mask_bad_instances(res, ("weights", "intercept"))
-        return res
+        return self._reader_call("mk_observation_weights", prob, res, ctypes.byref(req), mask=("weights", "intercept"))
 
     # ------------------------------------------------------------------ intervention effects by GLS
     EFFECT_KINDS = {"level": 0, "ramp": 1}   # MK_EFFECT_LEVEL / MK_EFFECT_RAMP
@@ -1037,17 +1037,12 @@ class BatchedKalman:
     def regression_supported(self):
         """True when ``regression`` serves this engine's shape (C ABI ``mk_regression_work_stride`` > 0): N + K <= 64,
         specialised or size-generic kernels alike."""
-        return self._reader_stride(self._L.mk_regression_work_stride, False) > 0
-
-    def _regression_stride(self):
-        return self._reader_stride(self._L.mk_regression_work_stride, False,
-                                   "intervention effects serve shapes with N + K <= 64; (N=%s, K=%s) is not one")
+        return self._reader_stride("regression") > 0
 
     def _regression_shapes(self, B, M):
-        """name -> (logical shape, follows the engine's layout) of the float64 buffers of ``regression``."""
-        shapes = self._bt_shapes(B, _work=self._regression_stride())
-        shapes.update(beta=((B, M), False), cov=((B, M, M), False), gain=((B,), False), normal=((B, M + 1, M + 1), False))
-        return shapes
+        torch = _torch()
+        return self._reader_shapes(B, beta=(B, M), cov=(B, M, M), gain=(B,), normal=(B, M + 1, M + 1),
+                                   ints=dict(support=((B, M), torch.int64), dropped=((B,), torch.int32)))
 
     def _effect_table(self, effects):
         """``[R,M,4]`` int64 on the device from ``[R,M,4]`` or ``[M,4]`` (shared by the records)."""
@@ -1063,14 +1058,10 @@ class BatchedKalman:
     def alloc_regression(self, B, M):
         """Buffers of ``regression`` for B instances and M effects per record (the forward pass's workspace with the gain tape +
         the outputs), for callers that run it repeatedly (pass them back as ``buffers=``)."""
-        torch = _torch()
         M = int(M)
         if not 1 <= M <= int(self._L.mk_regression_max_effects()):
             raise ValueError("M must be in 1..%d" % int(self._L.mk_regression_max_effects()))
-        res = self._reader_buffers(None, self._regression_shapes(B, M), "alloc_regression", sep=", ")
-        res["support"] = torch.empty((B, M), dtype=torch.int64, device=self.device)
-        res["dropped"] = torch.empty(B, dtype=torch.int32, device=self.device)
-        return res
+        return self._reader_buffers("regression", None, self._regression_shapes(B, M))
 
     def regression(self, phi, q, effects, t_first=1, x0=None, P0=None, buffers=None):
         """INTERVENTION EFFECTS by GLS for B instances (C ABI ``mk_regression``; de Jong's augmented filter): level shifts,
@@ -1086,31 +1077,19 @@ class BatchedKalman:
         ``status`` (the filter's MK_FLAG_* bits); the rows of an instance whose status carries ``FLAG_NONPOSITIVE_F`` are NaN.
         Four launches (the recording forward pass, a clear, the gain writer, the replay); an instance's outputs do not depend on
         the batch, bit for bit."""
-        torch = _torch()
         t_first = int(t_first)
         if t_first < 0:
             raise ValueError("t_first must be >= 0")
-        self._regression_stride()
+        stride = self._reader_stride("regression", refuse=True)
         ef = self._effect_table(effects)
         M = int(ef.shape[1])
         prob, keep, B = self._problem(phi, q, 0, x0, P0)
-        res = self._reader_buffers(buffers, self._regression_shapes(B, M), "alloc_regression", sep=", ")
-        for key, shape, dtype in (("support", (B, M), torch.int64), ("dropped", (B,), torch.int32)):
-            t = res.get(key)
-            if buffers is None:
-                t = res[key] = torch.empty(shape, dtype=dtype, device=self.device)
-            if t is None or tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous():
-                raise ValueError("buffers[%r] must be a contiguous %s tensor of shape %s (alloc_regression)" % (key, dtype, shape))
+        res = self._reader_buffers("regression", buffers, self._regression_shapes(B, M), stride)
         req = RegressionRequest()
         req.n_effects, req.t_first, req.d_effects = M, t_first, ef.data_ptr()
-        for field, key in (("d_beta", "beta"), ("d_cov", "cov"), ("d_gain", "gain"), ("d_normal", "normal"), ("d_support", "support"),
-                           ("d_dropped", "dropped")):
-            setattr(req, field, res[key].data_ptr())
-        self._bind_stream()
-        check(self._L.mk_regression(self._ctx, ctypes.byref(prob), self._p(res["_work"]), 1 if self.time_major else 0,
-                                    ctypes.byref(req), self._p(res["status"])))
-        self._mask_bad_instances(res, ("beta", "cov", "gain", "normal"))
-        return res
+        for key in ("beta", "cov", "gain", "normal", "support", "dropped"):
+            setattr(req, "d_" + key, res[key].data_ptr())
+        return self._reader_call("mk_regression", prob, res, ctypes.byref(req), mask=("beta", "cov", "gain", "normal"))
 
     # ------------------------------------------------------------------ per-step scores by the tangent filter
     _SCORE_OUTPUTS = ("score", "grad", "count", "opg", "cusum")
@@ -1119,29 +1098,17 @@ class BatchedKalman:
     def scores_supported(self):
         """True when ``scores`` serves this engine (C ABI ``mk_scores_work_stride`` > 0): N + K <= 64, specialised or
         size-generic kernels alike, full-square records."""
-        return not self.packed_sym and self._reader_stride(self._L.mk_scores_work_stride, False) > 0
-
-    def _scores_stride(self):
-        if self.packed_sym:
-            raise MetranHipError("libmetran_hip error -2 (MK_ERR_SHAPE): the scores read full-square records; this engine was "
-                                 "created with packed_sym=True")
-        return self._reader_stride(self._L.mk_scores_work_stride, False,
-                                   "per-step scores serve shapes with N + K <= 64; (N=%s, K=%s) is not one")
+        return self._reader_stride("scores") > 0
 
     def _scores_shapes(self, B):
-        """name -> (logical shape, follows the engine's layout) of the float64 buffers of ``scores``."""
         n = self.n
-        shapes = self._bt_shapes(B, _work=self._scores_stride(), score=n)
-        shapes.update(grad=((B, n), False), opg=((B, n, n), False), cusum=((B, n, n), False))
-        return shapes
+        return self._reader_shapes(B, bt=dict(score=n), grad=(B, n), opg=(B, n, n), cusum=(B, n, n),
+                                   ints=dict(count=((B,), _torch().int64)))
 
     def alloc_scores(self, B):
         """Buffers of ``scores`` for B instances (the forward pass's workspace with the gain tape and the innovations + the
         outputs), for callers that run it repeatedly (pass them back as ``buffers=``)."""
-        torch = _torch()
-        res = self._reader_buffers(None, self._scores_shapes(B), "alloc_scores", sep=", ")
-        res["count"] = torch.empty(B, dtype=torch.int64, device=self.device)
-        return res
+        return self._reader_buffers("scores", None, self._scores_shapes(B))
 
     def scores(self, phi, q, dphi, dq, t_first=1, x0=None, P0=None, buffers=None):
         """PER-STEP SCORES for B instances (C ABI ``mk_scores``; the forward-mode, tangent filter): ``score[b,t,p]`` is the
@@ -1155,28 +1122,18 @@ class BatchedKalman:
         ``metran_amd.scores.nyblom``) and ``status`` (the filter's MK_FLAG_* bits); the rows of an instance whose status carries
         ``FLAG_NONPOSITIVE_F`` are NaN.  Five launches (the recording forward pass, a clear, the gain writer, the tangent kernel,
         the sums); an instance's outputs do not depend on the batch, bit for bit."""
-        torch = _torch()
         t_first = int(t_first)
         if t_first < 0:
             raise ValueError("t_first must be >= 0")
-        self._scores_stride()
+        stride = self._reader_stride("scores", refuse=True)
         prob, keep, B = self._problem(phi, q, 0, x0, P0)
         dphi, dq = self._dev(dphi, (B, self.n), "dphi").contiguous(), self._dev(dq, (B, self.n), "dq").contiguous()
-        res = self._reader_buffers(buffers, self._scores_shapes(B), "alloc_scores", sep=", ")
-        t = res.get("count")
-        if buffers is None:
-            t = res["count"] = torch.empty(B, dtype=torch.int64, device=self.device)
-        if t is None or tuple(t.shape) != (B,) or t.dtype != torch.int64 or not t.is_contiguous():
-            raise ValueError("buffers['count'] must be a contiguous int64 tensor of shape (%d,) (alloc_scores)" % B)
+        res = self._reader_buffers("scores", buffers, self._scores_shapes(B), stride)
         req = ScoresRequest()
         req.d_dphi, req.d_dq, req.t_first = dphi.data_ptr(), dq.data_ptr(), t_first
         for key in self._SCORE_OUTPUTS:
             setattr(req, "d_" + key, res[key].data_ptr())
-        self._bind_stream()
-        check(self._L.mk_scores(self._ctx, ctypes.byref(prob), self._p(res["_work"]), 1 if self.time_major else 0,
-                                ctypes.byref(req), self._p(res["status"])))
-        self._mask_bad_instances(res, ("score", "grad", "opg", "cusum"))
-        return res
+        return self._reader_call("mk_scores", prob, res, ctypes.byref(req), mask=("score", "grad", "opg", "cusum"))
 
     def scores_alpha(self, alpha, dt=1.0, t_first=1):
         """``scores`` for Metran's parametrisation: ``phi, q`` by ``params_from_alpha`` and the derivatives with respect to alpha,
@@ -1199,20 +1156,10 @@ class BatchedKalman:
     def functionals_supported(self):
         """True when ``functionals`` serves this engine (C ABI ``mk_functionals_work_stride`` > 0): N + K <= 64, specialised or
         size-generic kernels alike, full-square records."""
-        return not self.packed_sym and self._reader_stride(self._L.mk_functionals_work_stride, False) > 0
-
-    def _functionals_stride(self):
-        if self.packed_sym:
-            raise MetranHipError("libmetran_hip error -2 (MK_ERR_SHAPE): window functionals read full-square records; this engine was "
-                                 "created with packed_sym=True")
-        return self._reader_stride(self._L.mk_functionals_work_stride, False,
-                                   "window functionals serve shapes with N + K <= 64; (N=%s, K=%s) is not one")
+        return self._reader_stride("functionals") > 0
 
     def _functionals_shapes(self, B, W, C):
-        """name -> (logical shape, follows the engine's layout) of the buffers of ``functionals``."""
-        shapes = self._bt_shapes(B, _work=self._functionals_stride())
-        shapes.update(mean=((B, W, C), False), var=((B, W, C), False))
-        return shapes
+        return self._reader_shapes(B, mean=(B, W, C), var=(B, W, C))
 
     def _functionals_counts(self, W, C):
         W, C, cmax = int(W), int(C), int(self._L.mk_functionals_max_contrasts())
@@ -1224,7 +1171,7 @@ class BatchedKalman:
         """Buffers of ``functionals`` for B instances, W windows and C contrasts per record (the workspace of the filtered and the
         smoothed records + the two outputs), for callers that run it repeatedly (pass them back as ``buffers=``)."""
         W, C = self._functionals_counts(W, C)
-        return self._reader_buffers(None, self._functionals_shapes(B, W, C), "alloc_functionals", sep=", ")
+        return self._reader_buffers("functionals", None, self._functionals_shapes(B, W, C))
 
     def functionals(self, phi, q, windows, contrasts=None, x0=None, P0=None, buffers=None):
         """EXACT posterior mean and variance of linear functionals of the smoothed signal for B instances (C ABI
@@ -1239,7 +1186,7 @@ class BatchedKalman:
         (the recording forward pass, the smoother, one walk per window); an instance's results do not depend on the batch, on the
         other windows or on the other contrasts, bit for bit."""
         torch = _torch()
-        self._functionals_stride()
+        stride = self._reader_stride("functionals", refuse=True)
         wn = torch.as_tensor(windows, dtype=torch.int64)
         if wn.ndim == 2:
             wn = wn[None].expand(self.R, -1, -1)
@@ -1256,15 +1203,12 @@ class BatchedKalman:
             ct = ct.to(self.device).contiguous()
         W, C = self._functionals_counts(wn.shape[1], self.N if ct is None else ct.shape[1])
         prob, keep, B = self._problem(phi, q, 0, x0, P0)
-        res = self._reader_buffers(buffers, self._functionals_shapes(B, W, C), "alloc_functionals", sep=", ")
+        res = self._reader_buffers("functionals", buffers, self._functionals_shapes(B, W, C), stride)
         req = FunctionalRequest()
         req.n_windows, req.n_contrasts = W, C
         req.d_windows, req.d_contrasts = wn.data_ptr(), None if ct is None else ct.data_ptr()
-        self._bind_stream()
-        check(self._L.mk_functionals(self._ctx, ctypes.byref(prob), self._p(res["_work"]), 1 if self.time_major else 0,
-                                     ctypes.byref(req), self._p(res["mean"]), self._p(res["var"]), self._p(res["status"])))
-        self._mask_bad_instances(res, ("mean", "var"))
-        return res
+        return self._reader_call("mk_functionals", prob, res, ctypes.byref(req), self._p(res["mean"]), self._p(res["var"]),
+                                 mask=("mean", "var"))
 
     def adjust_observations(self, effects, beta):
         """Subtract fitted intervention effects from the observations (C ABI ``mk_regression_adjust``): ``obs - sum_m beta_m x_m``
