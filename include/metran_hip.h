@@ -698,6 +698,59 @@ MK_API int64_t mk_scores_work_stride(int64_t N, int64_t K);
 MK_API int mk_scores(mk_context *ctx, const mk_problem *prob, double *d_work, int time_major, const mk_scores_request *req,
                      uint32_t *d_status);
 
+/* ---- leave-block-out predictions (block_kernels.hip) ----------------------------------------------------------------------------
+ * E[y_I | every observation except the block I] and its covariance V for a BLOCK I = the observed cells of one series on the steps
+ * [t0, t1): how well a gap of that length is filled from everything else (the single-cell case is mk_loo).  Model and filter order
+ * as in mk_innovations: prediction first, then the observed series of the step ascending, Z = [I | loadings]; per observed cell
+ * s = (t, j) the gain tape holds d_s = P z_j' and rf_s = 1 / f_s (mk_observation_weights), the innovations hold v_s; k_s = d_s rf_s.
+ *   With M = Sigma_y^-1 (the precision of the observed data vector) and u = M (y - mu), for any set I of observed cells
+ *     y_I - E[y_I | y_-I] = M_II^-1 u_I,      Cov[y_I | y_-I] = M_II^-1.
+ * u and the entries of M come from one backward walk: r = 0 and N = 0 (n x n) behind the last step; a cell that is not observed has
+ * d = 0 and rf = 0 and drops out arithmetically.  Per step t = T-1 .. 0, per observed cell s of the step with j DESCENDING:
+ *     1.  g = N k_s,   u_s = v_s rf_s - k_s'r,   M_ss = rf_s + k_s'g
+ *     2.  for every block cell c already passed (later in filter order), with its vector omega_c:
+ *             M_sc = -k_s'omega_c,   omega_c <- omega_c + z_j' M_sc
+ *     3.  if s belongs to the block: keep u_s and the row of M, start omega_s = M_ss z_j' - g
+ *     4.  r <- r + z_j' u_s,   N <- N - z_j g' - g z_j' + M_ss z_j' z_j
+ * and behind the cells of step t, at an empty step too, the pull-back through the prediction: r <- phi o r, N <- (phi phi') o N,
+ * omega_c <- phi o omega_c.  At the end, with e = M_II^-1 u_I:  prediction = y_I - e,  V = M_II^-1,  quad = u_I'e,
+ * log det V = -log det M_II.
+ *   mk_block_max_cells     64: the steps t1 - t0 of a block (one block cell per lane of a wavefront)
+ *   mk_block_work_stride   doubles per (instance, step) of d_work: the record, the gain tape and a row of N innovations (the scores'
+ *                          layout); 0 where the route does not serve the shape (N + K > 64)
+ *   mk_block_predict       Launches: the recording forward pass into d_work, the clear of the tape, innov_step_kernel writing the tape
+ *                          and v, then block_checkpoint_kernel (one lane group per instance: the (r, N) walk over the whole tape,
+ *                          storing (r, N) behind step t1 of every block into d_checkpoints) and block_walk_kernel (one wavefront per
+ *                          (instance, block): the steps t1-1 .. t0 from the checkpoint, then the solve: M_II scaled to unit diagonal,
+ *                          Cholesky in time order) -- timed in the smoother slot of mk_last_kernel_ms / mk_kernel_ms_totals.  Every sum
+ *                          has a fixed order: a block's outputs are bit-identical whatever the batch, the layout of d_work, the block
+ *                          list around it or its position in the list.
+ *                          d_means / d_vars hold NaN at the positions that are not observed or lie beyond t1.  A block without an
+ *                          observed cell has m = 0, NaN elsewhere and no flag; an unused slot (series < 0) an all-NaN row, m included.
+ *                          A pivot of the unit-diagonal M_II below 1e-12 (the regression's bound) makes the block DEGENERATE: its
+ *                          outputs except m are NaN and bit 0 of its flag is set; the other blocks are not affected.
+ *                          prob->warmup is ignored; d_status (may be NULL) receives the filter's MK_FLAG_* bits -- the outputs of an
+ *                          instance with MK_FLAG_NONPOSITIVE_F are not meaningful.
+ *   Served: every supported shape with N + K <= 64, under either kernel family; otherwise MK_ERR_SHAPE.  MK_ERR_INVALID (no
+ * launch): a missing pointer (all of the request's are required), n_blocks < 1, n_cells outside 1 .. mk_block_max_cells(), a buffer
+ * larger than the allocation it points into and, after one small copy of the descriptors to the host, a used slot with series >= N,
+ * t0 / t1 outside 0 <= t0 < t1 <= T, or t1 - t0 > n_cells. */
+typedef struct mk_block_request {
+    int64_t n_blocks;             /* W per record, >= 1 */
+    int64_t n_cells;              /* L: row length of the outputs, 1 .. mk_block_max_cells(); every block has t1 - t0 <= L */
+    const int64_t *d_blocks;      /* [n_records, W, 3] = (series, t0, t1), 0 <= t0 < t1 <= T; instance i uses record i % n_records;
+                                     a negative series marks an unused slot */
+    double *d_checkpoints;        /* workspace [B, W, n + n*n] */
+    double *d_means;              /* [B, W, L]: E[y | all but the block] * scale + offset at step t0 + c */
+    double *d_vars;               /* [B, W, L]: max(V_cc - obsvar_j, 0) * scale^2  (the projected state's variance, as mk_loo) */
+    double *d_summary;            /* [B, W, 4] = (m, quad, log det V, 1'V1 / m^2 * scale^2) */
+    uint32_t *d_flags;            /* [B, W]: bit 0 = degenerate block */
+} mk_block_request;
+MK_API int64_t mk_block_max_cells(void);
+MK_API int64_t mk_block_work_stride(int64_t N, int64_t K);
+MK_API int mk_block_predict(mk_context *ctx, const mk_problem *prob, double *d_work, int time_major, const mk_block_request *req,
+                            uint32_t *d_status);
+
 /* ---- exact window means, changes and contrasts of the smoothed signal (functional_kernels.hip) --------------------------------
  * The posterior mean and variance of LINEAR functionals of the smoothed path, per instance b (record r = b % n_records), window w
  * and contrast c:

@@ -130,6 +130,21 @@ class ScoresRequest(Structure):
     ]
 
 
+class BlockRequest(Structure):
+    """``mk_block_request`` (include/metran_hip.h)."""
+
+    _fields_ = [
+        ("n_blocks", c_int64),
+        ("n_cells", c_int64),
+        ("d_blocks", c_void_p),
+        ("d_checkpoints", c_void_p),
+        ("d_means", c_void_p),
+        ("d_vars", c_void_p),
+        ("d_summary", c_void_p),
+        ("d_flags", c_void_p),
+    ]
+
+
 class FunctionalRequest(Structure):
     """``mk_functional_request`` (include/metran_hip.h)."""
 
@@ -219,6 +234,9 @@ API = {
     "mk_scores_max_states": (c_int64, []),
     "mk_scores_work_stride": (c_int64, [c_int64, c_int64]),
     "mk_scores": (c_int, [c_void_p, POINTER(Problem), c_void_p, c_int, POINTER(ScoresRequest), c_void_p]),
+    "mk_block_max_cells": (c_int64, []),
+    "mk_block_work_stride": (c_int64, [c_int64, c_int64]),
+    "mk_block_predict": (c_int, [c_void_p, POINTER(Problem), c_void_p, c_int, POINTER(BlockRequest), c_void_p]),
     "mk_functionals_max_contrasts": (c_int64, []),
     "mk_functionals_work_stride": (c_int64, [c_int64, c_int64]),
     "mk_functionals": (c_int, [c_void_p, POINTER(Problem), c_void_p, c_int, POINTER(FunctionalRequest), c_void_p, c_void_p, c_void_p]),

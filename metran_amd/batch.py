@@ -15,6 +15,8 @@ number comes from the HIP kernels:
                                  forecast_skill)
     observation_weights      ->  which observations a smoothed value comes from (get_observation_weights, get_state_weights,
                                  get_weight_shares)
+    block_predict            ->  leave-block-out predictions: how well a gap of a given length is filled (get_gap_predictions,
+                                 gap_fill_skill)
     regression               ->  intervention effects by GLS: level shifts, outliers and trends of single series
                                  (fit_interventions, adjust_observations)
     scores_alpha             ->  per-step scores of the parameters by the tangent filter: OPG and robust standard errors,
@@ -30,7 +32,7 @@ table (``_KINDS``): ``_cache[kind] = (parameter set, {request: kept result})``. 
 parameter set -- different kinds may hold different ones -- and of that result only the keys its accessors read (the table's
 keep-list: never the forward pass's workspace, the records or the tape, which are hundreds of times the outputs), plus what
 the accessors derive from them once (``("simf", standardized)``, ``("decomp", standardized)``).  The kinds with a request
-(``forecast``, ``weights``, ``regress``, ``functionals``, ``scores``, ``hessian``) keep every request of their parameter set; another parameter set drops them all.  ``solve``,
+(``forecast``, ``weights``, ``regress``, ``functionals``, ``blocks``, ``scores``, ``hessian``) keep every request of their parameter set; another parameter set drops them all.  ``solve``,
 ``mask_observations``, ``unmask_observations``, ``adjust_observations`` and ``unadjust_observations`` clear the cache.  So asking for another series, the variances after the
 means, or the decomposition after the simulation does not launch anything.  The draws and their window statistics are not
 cached: an ensemble is the size of the thing it summarises.
@@ -85,6 +87,28 @@ def _functionals(mb, phi, q, request):
         mb.kf.set_scaling(mb._std, mb._mean)
 
 
+def _blocks(mb, phi, q, request):
+    """request = the block table as nested tuples [R][W][3]; original units (the facade's scaling is set)."""
+    return mb.kf.block_predict(phi, q, np.asarray(request, dtype=np.int64).reshape(mb.R, -1, 3))
+
+
+def _blocks_that_fit(kf, W, L, budget=None):
+    """How many instances one ``block_predict`` call can take so that its workspace, checkpoints and outputs stay within
+    ``budget`` bytes (None: 0.8 of the free device memory, as ``calibrate._grad_sets_that_fit`` has it).  Raises when not one fits."""
+    import torch
+
+    n = kf.N + kf.K
+    per_instance = 8.0 * (W * (n + n * n + 2 * L + 4.5) + kf.T * kf._reader_stride("blocks", refuse=True))
+    if budget is None:
+        dev = kf.device
+        budget = 0.8 * float(torch.cuda.mem_get_info(dev)[0]) if getattr(dev, "type", "cpu") == "cuda" else float("inf")
+    fit = int(min(kf.R, budget // per_instance))
+    if fit < 1:
+        raise MemoryError("leave-block-out predictions of %d blocks per model need %.3g bytes per model; the budget is %.3g" % (
+            W, per_instance, budget))
+    return fit
+
+
 def _scores(mb, alpha, request):
     """request = t_first.  The derivatives are Metran's, with respect to alpha: the engine forms them from the parameter set itself."""
     return mb.kf.scores_alpha(alpha, dt=mb.dt, t_first=request)
@@ -134,6 +158,8 @@ _FIT_KINDS = {
     "regress": (_regress, False, ("beta", "cov", "gain", "normal", "support", "dropped", "obj")),
     # exact moments of linear functionals of the smoothed signal, in the units the request names
     "functionals": (_functionals, False, ("mean", "var")),
+    # leave-block-out predictions of the requested gaps, original units
+    "blocks": (_blocks, True, ("means", "vars", "summary", "flags")),
 }
 # The kinds whose engine call takes the parameter set itself, alpha, not (phi, q): kind -> (engine call (facade, alpha, request),
 # keys of the result that are kept).  The same cache and the same status check, through ``MetranBatch._run``.
@@ -419,6 +445,163 @@ class MetranBatch:
         means, variances = self._loo(alpha, True)
         obs = self.kf.obs
         return torch.where(torch.isfinite(obs), (obs - means) / torch.sqrt(variances), torch.full_like(means, float("nan")))
+
+    # ------------------------------------------------------------------ leave-block-out predictions (gap filling)
+    def get_gap_predictions(self, gaps, alpha=None, standardized=False):
+        """How well GAPS would be filled: for every gap ``(model, series name, start, end)`` -- start and end timestamps on the
+        model's index or integer steps, end exclusive, None = the end of the record -- the observations inside it are predicted
+        from every observation OUTSIDE it (``BatchedKalman.block_predict``; parameters held fixed), which is what
+        ``mask_observations`` of the gap followed by ``get_simulation`` gives there, for all gaps in one pass.  Returns a
+        DataFrame with one row per observed cell of a gap, indexed (model, series, gap, time): ``observed``, ``predicted`` and
+        ``stderr`` (of the projected state, as ``get_loo_simulation``'s band) in ORIGINAL units, or standardised ones.
+        ``frame.attrs["gaps"]`` has one row per gap: ``n_obs``, ``quad`` (the errors' quadratic form in their covariance),
+        ``logdet`` and ``degenerate``.  A gap may span at most ``kf.block_max_cells`` = 64 steps."""
+        from pandas import DataFrame, MultiIndex
+
+        limit = int(self.kf.block_max_cells)
+        per_model = [[] for _ in range(self.R)]
+        for model, name, start, end in gaps:
+            r = int(model) - self.shard[0]
+            if not 0 <= r < self.R:
+                raise IndexError("model %s is not one of this batch" % (model,))
+            t0, t1 = self._effect_step(r, start), self._effect_step(r, end, end=True)
+            if not t0 < t1:
+                raise ValueError("a gap must end after it starts (model %s, series %s)" % (model, name))
+            if t1 - t0 > limit:
+                raise ValueError("a gap of %d steps is longer than the limit of %d steps (model %s, series %s)" % (t1 - t0, limit, model, name))
+            per_model[r].append((self._series(r, name), t0, t1))
+        W = max(len(b) for b in per_model) if per_model else 0
+        if W < 1:
+            raise ValueError("gaps must name at least one gap")
+        table = tuple(tuple(b + [(-1, 0, 0)] * (W - len(b))) for b in per_model)   # unused slots for the models with fewer
+        out = self._run("blocks", alpha, table)
+        means, variances = out["means"].cpu().numpy(), out["vars"].cpu().numpy()
+        summary, flags = out["summary"].cpu().numpy(), out["flags"].cpu().numpy()
+        obs, std, mean = self.kf.obs.cpu().numpy(), self._std.cpu().numpy(), self._mean.cpu().numpy()
+        rows, labels, grows, glabels = [], [], [], []
+        for r, blocks in enumerate(per_model):
+            index = self.batch.index[r]
+            for w, (j, t0, t1) in enumerate(blocks):
+                name = self.batch.names[r][j]
+                glabels.append((r + self.shard[0], name, w))
+                grows.append({"start": index[t0], "steps": t1 - t0, "n_obs": int(summary[r, w, 0]), "quad": summary[r, w, 1],
+                              "logdet": summary[r, w, 2], "degenerate": bool(flags[r, w] & 1)})
+                for c in range(t1 - t0):
+                    y = obs[r, t0 + c, j]
+                    if not np.isfinite(y):
+                        continue
+                    m, v = means[r, w, c], variances[r, w, c]
+                    if standardized:
+                        m, v = (m - mean[r, j]) / std[r, j], v / std[r, j] ** 2
+                    else:
+                        y = y * std[r, j] + mean[r, j]
+                    labels.append((r + self.shard[0], name, w, index[t0 + c]))
+                    rows.append({"observed": y, "predicted": m, "stderr": np.sqrt(v)})
+        frame = DataFrame(rows, columns=["observed", "predicted", "stderr"],
+                          index=MultiIndex.from_tuples(labels, names=["model", "series", "gap", "time"]))
+        frame.attrs["gaps"] = DataFrame(grows, index=MultiIndex.from_tuples(glabels, names=["model", "series", "gap"]))
+        return frame
+
+    def gap_fill_skill(self, lengths=(7, 30), alpha=None, t_first=1, coverage=0.95, budget=None):
+        """GAP-FILLING SKILL by gap length: every series is tiled with consecutive blocks of ``length`` steps from ``t_first``
+        (the last block of a record may be shorter; blocks without an observation are skipped), each block is predicted from
+        everything outside it (``BatchedKalman.block_predict``; length 1 is ``loo_predict``) and the errors are summarised per
+        (model, series, length): ``n_blocks``, ``n_cells``; ``bias`` = mean error and ``rmse`` in ORIGINAL units; ``msse`` = the
+        mean over the blocks of quad / m, quad the errors' quadratic form in their joint covariance and m the block's cells
+        (about 1 for an adequate model); ``coverage`` = the share of the cells inside the central ``coverage`` band;
+        ``log_score`` = the mean of (m log 2 pi + log det V + quad) / m in standardised units; and ``rmse_loo``, the same
+        cells' leave-one-out error (``get_deletion_residuals``' route) -- by what factor leave-one-out flatters the filling
+        of a gap of that length.  NaN where ``n_blocks`` = 0.  The models are taken in chunks whose checkpoints and outputs
+        stay within ``budget`` bytes (default: 0.8 of the free device memory); the reduction runs on the device."""
+        import torch
+        from pandas import DataFrame, concat
+        from scipy.stats import norm
+
+        t_first, limit = int(t_first), int(self.kf.block_max_cells)
+        lengths = [int(h) for h in lengths]
+        if t_first < 0 or not lengths or min(lengths) < 1 or max(lengths) > limit:
+            raise ValueError("t_first must be >= 0 and the lengths in 1..%d" % limit)
+        if not 0.0 < coverage < 1.0:
+            raise ValueError("coverage must be between 0 and 1")
+        a = self._alpha(alpha)
+        zq = float(norm.ppf(0.5 + coverage / 2.0))
+        kf, R, N, T = self.kf, self.R, self.N, self.T
+        dev = a.device
+        obs = kf.obs.to(dev)                                                    # standardised records [R,T,N]
+        seen_host = torch.isfinite(obs).cpu().numpy()
+        std = self._std.to(dev)
+        rec_len = np.asarray(self.batch.lengths, dtype=np.int64)
+        lm, lv = self._loo(a, True)                                            # standardised leave-one-out moments
+        loo_err = torch.where(torch.isfinite(obs), obs - lm, torch.zeros_like(obs))
+        frames = []
+        for h in lengths:
+            # the blocks of every model, series by series in slots of their own (those without an observation are left out, a
+            # series with fewer blocks has unused slots): the sums over a series' slots have a fixed order
+            per_series = [[[(j, t0, min(t0 + h, int(rec_len[r]))) for t0 in range(t_first, int(rec_len[r]), h)
+                            if seen_host[r, t0:min(t0 + h, int(rec_len[r])), j].any()] for j in range(N)] for r in range(R)]
+            Ws = max(1, max(len(b) for blocks in per_series for b in blocks))
+            W = N * Ws
+            table = torch.tensor([[b + [(-1, 0, 0)] * (Ws - len(b)) for b in blocks] for blocks in per_series],
+                                 dtype=torch.int64).reshape(R, W, 3)
+            tab = table.to(dev)
+            used = tab[..., 0] >= 0
+            js = tab[..., 0].clamp_min(0)
+            steps = tab[..., 1, None] + torch.arange(h, device=dev)[None, None, :]                 # [R,W,h]
+            inside = used[..., None] & (steps < tab[..., 2, None])
+            tt = steps.clamp_max(T - 1)
+            rr = torch.arange(R, device=dev)[:, None, None].expand_as(tt)
+            y = obs[rr, tt, js[..., None].expand_as(tt)]
+            cell = inside & torch.isfinite(y)
+            if h == 1:    # one-cell blocks: the leave-one-out predictions
+                pm = lm[rr, tt, js[..., None].expand_as(tt)]
+                pv = lv[rr, tt, js[..., None].expand_as(tt)]
+                rv = torch.zeros((R, N), dtype=obs.dtype, device=dev) if getattr(kf, "obsvar", None) is None else kf.obsvar.to(dev)
+                vfull = pv[..., 0] + rv[torch.arange(R, device=dev)[:, None], js]
+                e0 = torch.where(cell[..., 0], y[..., 0] - pm[..., 0], torch.zeros_like(vfull))
+                m = cell[..., 0].to(obs.dtype)
+                quad, logdet = e0 * e0 / vfull, torch.log(vfull)
+            else:
+                pm = torch.full((R, W, h), float("nan"), dtype=obs.dtype, device=dev)
+                pv = torch.full_like(pm, float("nan"))
+                summary = torch.empty((R, W, 4), dtype=obs.dtype, device=dev)
+                chunk = _blocks_that_fit(kf, W, h, budget)
+                kf.set_scaling(None, None)                                     # standardised units; the facade's scaling is put back
+                try:
+                    phi, q = kf.params_from_alpha(a, dt=self.dt)
+                    for r0 in range(0, R, chunk):
+                        r1 = min(R, r0 + chunk)
+                        whole = r0 == 0 and r1 == R
+                        sub = kf if whole else kf.subset(np.arange(r0, r1))
+                        out = sub.block_predict(phi[r0:r1], q[r0:r1], table[r0:r1])
+                        check_status(out["status"].reshape(-1), "MetranBatch(blocks)")
+                        width = min(h, int(out["means"].shape[2]))       # the longest block of the chunk
+                        pm[r0:r1, :, :width], pv[r0:r1, :, :width] = out["means"][..., :width], out["vars"][..., :width]
+                        summary[r0:r1] = out["summary"]
+                finally:
+                    kf.set_scaling(self._std, self._mean)
+                m, quad, logdet = summary[..., 0], summary[..., 1], summary[..., 2]
+            good = used & (m > 0) & torch.isfinite(quad)                       # a degenerate block is left out
+            cell = cell & good[..., None]
+            zero = torch.zeros_like(y)
+            err = torch.where(cell, y - pm, zero)
+            inband = (cell & (err.abs() <= zq * torch.sqrt(torch.where(cell, pv, zero + 1.0)))).to(obs.dtype)
+            le = torch.where(cell, loo_err[rr, tt, js[..., None].expand_as(tt)], zero)
+            mm = torch.where(good, m, torch.ones_like(m))
+            per_block = torch.stack([good.to(obs.dtype), cell.sum(2).to(obs.dtype), err.sum(2), (err * err).sum(2),
+                                     torch.where(good, quad / mm, zero[..., 0]), inband.sum(2),
+                                     torch.where(good, (mm * np.log(2.0 * np.pi) + logdet + quad) / mm, zero[..., 0]), (le * le).sum(2)], dim=2)
+            sums = torch.where(used[..., None], per_block, torch.zeros_like(per_block)).reshape(R, N, Ws, 8).sum(2)
+            nb = sums[..., 0]
+            nbn = torch.where(nb > 0, nb, torch.full_like(nb, float("nan")))
+            nc = torch.where(sums[..., 1] > 0, sums[..., 1], torch.full_like(nb, float("nan")))
+            cols = torch.stack([nb, sums[..., 1], sums[..., 2] / nc * std, torch.sqrt(sums[..., 3] / nc) * std, sums[..., 4] / nbn,
+                                sums[..., 5] / nc, sums[..., 6] / nbn, torch.sqrt(sums[..., 7] / nc) * std], dim=2).cpu().numpy().reshape(R * N, 8)
+            index = self._rows(lambda r, h=h: ((name, h) for name in self.batch.names[r]), ["series", "length"])
+            frames.append(DataFrame({"n_blocks": cols[:, 0].astype(np.int64), "n_cells": cols[:, 1].astype(np.int64), "bias": cols[:, 2],
+                                     "rmse": cols[:, 3], "msse": cols[:, 4], "coverage": cols[:, 5], "log_score": cols[:, 6],
+                                     "rmse_loo": cols[:, 7]}, index=index))
+        order = self._rows(lambda r: ((name, h) for name in self.batch.names[r] for h in lengths), ["series", "length"])
+        return concat(frames).reindex(order)
 
     # ------------------------------------------------------------------ one-step-ahead innovations (model adequacy)
     def get_innovations(self, alpha=None, standardized=True):

@@ -12,6 +12,7 @@
 #include <vector>
 #include <new>
 
+#include "block_kernels.h"
 #include "draw_kernels.h"
 #include "ensemble_kernels.h"
 #include "forecast_kernels.h"
@@ -1865,6 +1866,82 @@ MK_API int mk_scores(mk_context *ctx, const mk_problem *p, double *d_work, int t
         if (int rc = gain_tape_stage(ctx, p, d_work, w, time_major, d_work + w.innov)) return rc;
         MK_HIP(mk::launch_score_tangent(a, ctx->stream));
         MK_HIP(mk::launch_score_stats(a, ctx->stream));
+        return MK_OK;
+    });
+}
+
+// ---- leave-block-out predictions (block_kernels.hip) ----
+MK_API int64_t mk_block_max_cells(void) { return mk::block_max_cells; }
+
+MK_API int64_t mk_block_work_stride(int64_t N, int64_t K)
+{
+    static_assert(mk::block_max_states == mk::score_max_states, "the blocks run on the scores' workspace");
+    return mk_scores_work_stride(N, K);
+}
+
+// the blocks of a request, copied to the host: a slot in use must name a series and a step range that exist and fit a row
+static int check_blocks(mk_context *ctx, const int64_t *d_blocks, int64_t R, int64_t W, int64_t L, int64_t T, int64_t N)
+{
+    std::vector<int64_t> h((size_t)(R * W * 3));
+    MK_HIP(hipMemcpyAsync(h.data(), d_blocks, sizeof(int64_t) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
+    MK_HIP(hipStreamSynchronize(ctx->stream));
+    for (int64_t i = 0; i < R * W; ++i) {
+        const int64_t *e = &h[(size_t)i * 3];
+        if (e[0] < 0) continue;
+        if (e[0] >= N)
+            return fail(MK_ERR_INVALID, "mk_block_predict: d_blocks[%lld, %lld]: series %lld is outside 0 .. N - 1 = %lld", (long long)(i / W),
+                        (long long)(i % W), (long long)e[0], (long long)(N - 1));
+        if (!(0 <= e[1] && e[1] < e[2] && e[2] <= T))
+            return fail(MK_ERR_INVALID, "mk_block_predict: d_blocks[%lld, %lld]: need 0 <= t0 < t1 <= T = %lld (got t0 = %lld, t1 = %lld)",
+                        (long long)(i / W), (long long)(i % W), (long long)T, (long long)e[1], (long long)e[2]);
+        if (e[2] - e[1] > L)
+            return fail(MK_ERR_INVALID, "mk_block_predict: d_blocks[%lld, %lld]: t1 - t0 = %lld is more than n_cells = %lld", (long long)(i / W),
+                        (long long)(i % W), (long long)(e[2] - e[1]), (long long)L);
+    }
+    return MK_OK;
+}
+
+MK_API int mk_block_predict(mk_context *ctx, const mk_problem *p, double *d_work, int time_major, const mk_block_request *req,
+                            uint32_t *d_status)
+{
+    if (int rc = reader_preamble(ctx, "mk_block_predict", "mk_block_request", p, mk::block_max_states, req, d_work)) return rc;
+    if (!req->d_blocks || !req->d_checkpoints || !req->d_means || !req->d_vars || !req->d_summary || !req->d_flags)
+        return fail(MK_ERR_INVALID, "mk_block_predict: d_blocks, d_checkpoints, d_means, d_vars, d_summary and d_flags are required");
+    if (req->n_blocks < 1) return fail(MK_ERR_INVALID, "mk_block_predict: need n_blocks >= 1 (got %lld)", (long long)req->n_blocks);
+    if (req->n_cells < 1 || req->n_cells > mk::block_max_cells)
+        return fail(MK_ERR_INVALID, "mk_block_predict: need 1 <= n_cells <= %d (got %lld)", mk::block_max_cells, (long long)req->n_cells);
+    if (!p->d_obs || !p->d_loadings) return fail(MK_ERR_INVALID, "d_obs and d_loadings are required");
+    if (!mk_block_work_stride(p->N, p->K)) return too_many_states("mk_block_predict", p, mk::block_max_states);
+    const int64_t B = p->n_instances, W = req->n_blocks, L = req->n_cells, n = p->N + p->K;
+    const work_layout w = layout_of(WORK_SCORES, p->N, p->K, B, p->T);
+    static_assert(sizeof(int64_t) == sizeof(double), "buffers_fit counts 8-byte words");
+    const device_buffer bufs[7] = {{d_work, B * p->T * w.stride, "d_work (n_instances * T * mk_block_work_stride(N, K) doubles)"},
+                                   {req->d_blocks, p->n_records * W * 3, "d_blocks (n_records * n_blocks * 3 64-bit integers)"},
+                                   {req->d_checkpoints, B * W * (n + n * n), "d_checkpoints (n_instances * n_blocks * (n + n^2) doubles)"},
+                                   {req->d_means, B * W * L, "d_means (n_instances * n_blocks * n_cells doubles)"},
+                                   {req->d_vars, B * W * L, "d_vars (n_instances * n_blocks * n_cells doubles)"},
+                                   {req->d_summary, B * W * 4, "d_summary (n_instances * n_blocks * 4 doubles)"},
+                                   {req->d_flags, (B * W + 1) / 2, "d_flags (n_instances * n_blocks 32-bit words)"}};
+    if (int rc = buffers_fit("mk_block_predict", bufs, 7)) return rc;
+    if (int rc = check_blocks(ctx, req->d_blocks, p->n_records, W, L, p->T, p->N)) return rc;
+    if (int rc = record_pass(ctx, p, d_work, w.rs, time_major, d_status)) return rc;
+    mk::BlockArgs a = reader_args<mk::BlockArgs>(p, d_work, w.rs, time_major); // the walks read the tape, not the records
+    fill_scaling(a, p);
+    a.W = W;
+    a.L = L;
+    a.gs = w.gs;
+    a.gain = d_work + w.tape;
+    a.v = d_work + w.innov;
+    a.blocks = req->d_blocks;
+    a.checkpoints = req->d_checkpoints;
+    a.means = req->d_means;
+    a.vars = req->d_vars;
+    a.summary = req->d_summary;
+    a.flags = req->d_flags;
+    return timed_launches(ctx, [&]() -> int {
+        if (int rc = gain_tape_stage(ctx, p, d_work, w, time_major, d_work + w.innov)) return rc;
+        MK_HIP(mk::launch_block_checkpoint(a, ctx->stream));
+        MK_HIP(mk::launch_block_walk(a, ctx->stream));
         return MK_OK;
     });
 }

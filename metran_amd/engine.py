@@ -14,7 +14,7 @@ import logging
 import numpy as np
 
 from . import _lib
-from ._lib import ForecastRequest, FunctionalRequest, MetranHipError, Outputs, Problem, RegressionRequest, ScoresRequest, WeightsRequest, check
+from ._lib import BlockRequest, ForecastRequest, FunctionalRequest, MetranHipError, Outputs, Problem, RegressionRequest, ScoresRequest, WeightsRequest, check
 
 logger = logging.getLogger(__name__)
 
@@ -709,7 +709,7 @@ class BatchedKalman:
         return res
 
     # ------------------------------------------------------------------ the record readers: one scaffold
-    # loo_predict, disturbances, innovations, forecast, observation_weights, regression, scores and functionals (which also runs
+    # loo_predict, disturbances, innovations, forecast, observation_weights, regression, scores, block_predict and functionals (which also runs
     # the smoother) run the recording forward pass into a workspace ("_work") and kernels that read its filtered records.  What a
     # reader keeps to itself is the validation of its request, its shapes and its request struct; the table, _reader_stride,
     # _reader_shapes, _reader_buffers and _reader_call are the rest.
@@ -725,12 +725,14 @@ class BatchedKalman:
                     "alloc_observation_weights"),
         "regression": ("mk_regression_work_stride", False, None, "intervention effects serve shapes with N + K <= 64", "alloc_regression"),
         "scores": ("mk_scores_work_stride", False, "the scores", "per-step scores serve shapes with N + K <= 64", "alloc_scores"),
+        "blocks": ("mk_block_work_stride", False, "leave-block-out predictions", "leave-block-out predictions serve shapes with N + K <= 64",
+                   "alloc_block_predict"),
         "functionals": ("mk_functionals_work_stride", False, "window functionals", "window functionals serve shapes with N + K <= 64",
                         "alloc_functionals"),
     }
 
     # NOTE: loo_supported() and disturbances_supported() are methods, innovations_supported, forecast_supported,
-    # observation_weights_supported, regression_supported, scores_supported and functionals_supported properties -- an
+    # observation_weights_supported, regression_supported, scores_supported, block_predict_supported and functionals_supported properties -- an
     # inconsistency of the public API that is kept.
     def _reader_stride(self, name, refuse=False):
         """Doubles per (instance, step) of the workspace of the record reader ``name``; where the engine is not served 0, or with
@@ -1150,6 +1152,81 @@ class BatchedKalman:
         dphi = phi * float(dt) / (alpha * alpha)
         dq = -2.0 * phi * dphi * c.repeat(B // self.R, 1)
         return self.scores(phi, q, dphi, dq, t_first=t_first)
+
+    # ------------------------------------------------------------------ leave-block-out predictions
+    _BLOCK_OUTPUTS = ("means", "vars", "summary", "flags")
+
+    @property
+    def block_predict_supported(self):
+        """True when ``block_predict`` serves this engine (C ABI ``mk_block_work_stride`` > 0): N + K <= 64, specialised or
+        size-generic kernels alike, full-square records."""
+        return self._reader_stride("blocks") > 0
+
+    @property
+    def block_max_cells(self):
+        """The largest number of steps of a block (C ABI ``mk_block_max_cells``)."""
+        return int(self._L.mk_block_max_cells())
+
+    def _block_shapes(self, B, W, L):
+        n = self.n
+        return self._reader_shapes(B, means=(B, W, L), vars=(B, W, L), summary=(B, W, 4), _checkpoints=(B, W, n + n * n),
+                                   ints=dict(flags=((B, W), _torch().int32)))
+
+    def _block_table(self, blocks):
+        """``[R,W,3]`` int64 on the host from ``[R,W,3]`` or ``[W,3]`` (shared by the records), validated."""
+        torch = _torch()
+        bl = torch.as_tensor(blocks, dtype=torch.int64).cpu()
+        if bl.ndim == 2:
+            bl = bl[None].expand(self.R, -1, -1)
+        if bl.ndim != 3 or bl.shape[0] != self.R or bl.shape[1] < 1 or bl.shape[2] != 3:
+            raise ValueError("blocks must be [%d,W,3] (or [W,3]) integers (series, t0, t1), W >= 1" % self.R)
+        used = bl[..., 0] >= 0
+        if bool((used & (bl[..., 0] >= self.N)).any()):
+            raise ValueError("blocks: a series is outside 0 .. N - 1 = %d" % (self.N - 1))
+        if bool((used & ~((bl[..., 1] >= 0) & (bl[..., 1] < bl[..., 2]) & (bl[..., 2] <= self.T))).any()):
+            raise ValueError("blocks: need 0 <= t0 < t1 <= T = %d" % self.T)
+        length = int(((bl[..., 2] - bl[..., 1]) * used).max()) if bool(used.any()) else 1
+        if length > self.block_max_cells:
+            raise ValueError("blocks: a block of %d steps is longer than the limit of %d" % (length, self.block_max_cells))
+        return bl.contiguous(), max(length, 1)
+
+    def alloc_block_predict(self, B, W, L):
+        """Buffers of ``block_predict`` for B instances, W blocks per record and rows of L cells (the forward pass's workspace
+        with the gain tape and the innovations, the checkpoints + the outputs), for callers that run it repeatedly (pass them
+        back as ``buffers=``)."""
+        W, L = int(W), int(L)
+        if W < 1 or not 1 <= L <= self.block_max_cells:
+            raise ValueError("W must be >= 1 and L in 1..%d" % self.block_max_cells)
+        return self._reader_buffers("blocks", None, self._block_shapes(B, W, L))
+
+    def block_predict(self, phi, q, blocks, x0=None, P0=None, buffers=None):
+        """LEAVE-BLOCK-OUT PREDICTIONS for B instances (C ABI ``mk_block_predict``): for every block ``(series, t0, t1)`` --
+        ``blocks`` is ``[R,W,3]`` integers (or ``[W,3]``, shared by the records), ``0 <= t0 < t1 <= T``, at most
+        ``block_max_cells`` = 64 steps, a negative series marks an unused slot, instance b uses the blocks of record ``b % R`` --
+        the prediction of the block's observed cells from EVERY observation outside the block, with its covariance V: how well a
+        gap of that length is filled.  Returns a dict with ``means [B,W,L]`` and ``vars [B,W,L]`` (L = the longest block, or the
+        row length of ``buffers``; position c is step t0 + c; the caller's units, ``vars`` without the observation variance, as
+        ``loo_predict``; NaN where the cell is not observed or beyond t1), ``summary [B,W,4]`` = (m observed cells, quad =
+        e'V^-1 e of the prediction errors e, log det V, 1'V1 / m^2 in the caller's units: the variance of the block's mean),
+        ``flags [B,W]`` (bit 0: the block is degenerate -- a pivot of the unit-diagonal precision block below 1e-12; its outputs
+        except m are NaN) and ``status`` (the filter's MK_FLAG_* bits); the rows of an instance whose status carries
+        ``FLAG_NONPOSITIVE_F`` are NaN.  quad and log det V are in the units of the standardised observations the filter runs on.
+        Five launches (the recording forward pass, a clear, the gain writer, the checkpoint walk, the block walk); a block's
+        outputs do not depend on the batch or on the other blocks, bit for bit."""
+        stride = self._reader_stride("blocks", refuse=True)
+        bl, length = self._block_table(blocks)
+        W = int(bl.shape[1])
+        prob, keep, B = self._problem(phi, q, 0, x0, P0)
+        L = int(buffers["means"].shape[2]) if buffers is not None and hasattr(buffers.get("means"), "shape") and buffers["means"].ndim == 3 else length
+        if L < length:
+            raise ValueError("buffers hold rows of %d cells; a block has %d steps" % (L, length))
+        res = self._reader_buffers("blocks", buffers, self._block_shapes(B, W, L), stride)
+        bl = bl.to(self.device)
+        req = BlockRequest()
+        req.n_blocks, req.n_cells, req.d_blocks, req.d_checkpoints = W, L, bl.data_ptr(), res["_checkpoints"].data_ptr()
+        for key in self._BLOCK_OUTPUTS:
+            setattr(req, "d_" + key, res[key].data_ptr())
+        return self._reader_call("mk_block_predict", prob, res, ctypes.byref(req), mask=("means", "vars", "summary"))
 
     # ------------------------------------------------------------------ exact window means, changes and contrasts
     @property
