@@ -429,6 +429,35 @@ MK_API int mk_innovations(mk_context *ctx, const mk_problem *prob, double *d_wor
 MK_API int mk_innovation_stats(mk_context *ctx, int64_t B, int64_t T, int64_t N, int time_major, int64_t t_first, int64_t nlags,
                                const double *d_v, const double *d_f, double *d_stats);
 
+/* RESIDUAL DIAGNOSTICS of the standardised innovations e = v / sqrt(f) (d_v / d_f as written by mk_innovations, [B,T,N], or
+ * [T,B,N] with time_major): beside the whiteness of mk_innovation_stats, the two other standard checks -- normality and
+ * constant variance -- and the one a FACTOR model needs: are the innovations of different series uncorrelated with each other?
+ * A cell (t, j) is VALID when v is finite, f is finite and > 0 and t >= t_first (mk_innovation_stats' rule).  Per (instance,
+ * series), with t_1 < ... < t_m the valid cells and e_1 .. e_m their values:
+ *     mean = sum e_i / m,   d_i = e_i - mean,   S_k = sum d_i^k  (k = 2, 3, 4; sums, not divided),   h = (m + 1) / 3 (integer),
+ *     ss_first = sum_{i <= h} e_i^2,   ss_last = sum_{i > m - h} e_i^2     (raw e; thirds of the COMPACTED sequence of valid cells),
+ *     cusum = max_k |C_k|,  C_k = sum_{i <= k} d_i;      cusq = max_k |Q_k - (k / m) S2|,  Q_k = sum_{i <= k} d_i^2,
+ * cusum_t / cusq_t the calendar step t_k of the FIRST k that attains the maximum.
+ * mk_residual_series: d_stats [B,N,12] = [m, mean, S2, S3, S4, h, ss_first, ss_last, cusum, cusum_t, cusq, cusq_t]; for m = 0 the
+ * row is [0, NaN x 4, 0, NaN x 6]; for a constant series (S2 = 0) the raw sums are written as they are.
+ * mk_residual_cross: with e~[t,j] = d / sqrt(S2 / m) at the valid cells (mean, S2, m from d_stats, the rows mk_residual_series
+ * wrote for the same d_v, d_f and t_first), for the lags l = 0 .. nlags (0 <= nlags <= 32) and all ORDERED pairs (i, j)
+ *     d_counts[b,l,i,j] = n_ij(l) = the number of t for which both (t, i) and (t - l, j) are valid   (64-bit integers),
+ *     d_sums[b,l,i,j]   = s_ij(l) = sum of e~[t,i] e~[t-l,j] over those t,
+ * both [B,nlags+1,N,N].  Lags are CALENDAR steps here: two series share a clock, not a sequence of observed cells.  A pair in
+ * which either series has m = 0 or S2 = 0 gets n = 0 and s = NaN.  N <= 64.  Under the model r_ij(l) = s / n is approximately
+ * N(0, 1/n) for i != j or l > 0.
+ *   Every sum is taken in one fixed order that depends on T and the series' own cells alone.  mk_residual_series: 64 accumulators,
+ * accumulator l adding the cells of steps l, 64 + l, 128 + l, .. in ascending time, then summed once by a fixed tree (lanes l and
+ * l ^ 32, ^ 16, .. ^ 1); the running sums C_k and Q_k: a prefix scan over each tile of 64 steps plus the carry of the tiles
+ * before.  mk_residual_cross: ascending time into one accumulator per (lag, i, j).  So an instance's results are bit-identical
+ * whatever the batch around it and in either layout.  MK_ERR_INVALID (no launch) with a message that
+ * names the argument for a missing pointer, N > 64, nlags outside 0 .. 32 and a buffer larger than the allocation it points into. */
+MK_API int mk_residual_series(mk_context *ctx, int64_t B, int64_t T, int64_t N, int time_major, int64_t t_first, const double *d_v,
+                              const double *d_f, double *d_stats);
+MK_API int mk_residual_cross(mk_context *ctx, int64_t B, int64_t T, int64_t N, int time_major, int64_t t_first, int64_t nlags,
+                             const double *d_v, const double *d_f, const double *d_stats, int64_t *d_counts, double *d_sums);
+
 /* MULTI-STEP-AHEAD FORECASTS and FORECAST SKILL BY HORIZON (statsmodels' forecast / get_prediction, KFAS' predict): what the model
  * says about steps it has not seen, and how far ahead that is worth anything.  Model and units as in mk_innovations (Phi and Q
  * diagonal, Z = [I | Gamma], observation variances R_j, zero when d_obsvar is NULL; the filter's standardised units, scale /

@@ -222,6 +222,9 @@ API = {
     "mk_innovations_work_stride": (c_int64, [c_int64, c_int64]),
     "mk_innovations": (c_int, [c_void_p, POINTER(Problem), c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mk_innovation_stats": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "mk_residual_series": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
+    "mk_residual_cross": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p]),
     "mk_forecast_max_horizon": (c_int64, []),
     "mk_forecast_work_stride": (c_int64, [c_int64, c_int64]),
     "mk_forecast": (c_int, [c_void_p, POINTER(Problem), c_void_p, c_int, POINTER(ForecastRequest), c_void_p]),

@@ -649,6 +649,147 @@ class MetranBatch:
             frame["r%d" % l] = flat[:, 3 + l]
         return frame
 
+    # ------------------------------------------------------------------ residual diagnostics (normality, variance, cross-series)
+    def _residual_kept(self, alpha):
+        """``(cached "innov" result, the residual sums derived from it so far)``: a dict of its own, keyed by request and tied
+        to that very result -- when the cache replaces or drops the innovations (another parameter set, new observations) the
+        sums derived from the old ones go with them."""
+        out = self._run("innov", alpha)
+        kept = getattr(self, "_resid_kept", None)
+        if kept is None or kept[0] is not out:
+            kept = self._resid_kept = (out, {})
+        return out, kept[1]
+
+    def _residual_stats(self, alpha, t_first):
+        """``(cached "innov" result, BatchedKalman.residual_series of it)`` for the parameter set, one tensor per ``t_first``."""
+        out, kept = self._residual_kept(alpha)
+        key = ("series", int(t_first))
+        if key not in kept:
+            kept[key] = self.kf.residual_series(out["v"], out["f"], t_first=int(t_first))
+        return out, kept[key]
+
+    def _residual_cross(self, alpha, t_first, nlags):
+        """``(counts, sums)`` ``[R,nlags+1,N,N]`` of ``BatchedKalman.residual_cross`` as numpy arrays, kept the same way."""
+        out, stats = self._residual_stats(alpha, t_first)
+        kept = self._resid_kept[1]
+        key = ("cross", int(t_first), int(nlags))
+        if key not in kept:
+            counts, sums = self.kf.residual_cross(out["v"], out["f"], stats, nlags=int(nlags), t_first=int(t_first))
+            kept[key] = (counts.cpu().numpy(), sums.cpu().numpy())
+        return kept[key]
+
+    def _step_times(self, steps):
+        """Calendar steps ``[R*N]`` (-1: none) of every (model, series) row as time stamps of each model's own index."""
+        from pandas import DatetimeIndex, NaT
+
+        steps = np.asarray(steps).reshape(self.R, self.N)
+        return DatetimeIndex([self.batch.index[r][int(t)] if 0 <= t < len(self.batch.index[r]) else NaT
+                              for r in range(self.R) for t in steps[r]])
+
+    def test_normality(self, alpha=None, t_first=1):
+        """Jarque-Bera check of every series' standardised innovations ``e`` (statsmodels' ``test_normality``): DataFrame
+        indexed (model, series) with ``nobs`` (cells used: observed, ``t >= t_first``), ``skew = m3 / m2^1.5``, ``kurtosis =
+        m4 / m2^2`` (central moments with divisor m; 3 for a normal), ``JB = m / 6 (skew^2 + (kurtosis - 3)^2 / 4)`` and
+        ``pvalue = chi2.sf(JB, 2)``.  The chi-square law is asymptotic: with a few dozen cells the test is conservative.  NaN
+        where a series has fewer than 4 cells or does not vary."""
+        from pandas import DataFrame
+
+        from .residuals import normality
+
+        cols = normality(self._residual_stats(alpha, t_first)[1].cpu().numpy().reshape(self.R * self.N, 12))
+        return DataFrame(cols, index=self._rows(lambda r: ((name,) for name in self.batch.names[r]), ["series"]))
+
+    def test_heteroskedasticity(self, alpha=None, t_first=1):
+        """Is the variance of every series' standardised innovations ``e`` constant over the record?  DataFrame indexed (model,
+        series) with ``nobs``; the break-variance test of statsmodels / STAMP: ``h = (nobs + 1) // 3``, ``H`` = the sum of
+        ``e^2`` over the LAST ``h`` observed cells over that of the FIRST ``h`` (thirds of the sequence of observed cells, as
+        ``test_whiteness`` counts its lags) and the two-sided ``pvalue = 2 min(F.cdf(H, h, h), F.sf(H, h, h))``; and the two
+        running checks, with ``d = e - mean`` and ``s^2`` its variance (divisor m): ``cusum = max_k |sum_{i<=k} d_i| / sqrt(m
+        s^2)`` (a shift of the LEVEL) and ``cusumsq = sqrt(m / 2) max_k |sum_{i<=k} d_i^2 / (m s^2) - k / m|`` (a shift of the
+        VARIANCE, Brown-Durbin-Evans), each with the time stamp of the cell at which the excursion is largest (``cusum_time``,
+        ``cusumsq_time``, from the model's own index: where the break is) and ``cusum_pvalue`` / ``cusumsq_pvalue`` =
+        ``scipy.special.kolmogorov`` of the statistic, the law of the supremum of a Brownian bridge.  That limit is
+        ASYMPTOTIC and, for ``cusumsq``, assumes GAUSSIAN ``e``: on finite records both are conservative (they reject less
+        often than the level says).  NaN where ``h = 0``, the first third's sum is 0 or the series does not vary."""
+        from pandas import DataFrame
+
+        from .residuals import heteroskedasticity
+
+        c = heteroskedasticity(self._residual_stats(alpha, t_first)[1].cpu().numpy().reshape(self.R * self.N, 12))
+        frame = DataFrame({"nobs": c["nobs"], "h": c["h"], "H": c["H"], "pvalue": c["pvalue"],
+                           "cusum": c["cusum"], "cusum_time": self._step_times(c["cusum_step"]), "cusum_pvalue": c["cusum_pvalue"],
+                           "cusumsq": c["cusumsq"], "cusumsq_time": self._step_times(c["cusumsq_step"]),
+                           "cusumsq_pvalue": c["cusumsq_pvalue"]},
+                          index=self._rows(lambda r: ((name,) for name in self.batch.names[r]), ["series"]))
+        return frame
+
+    def test_cross_correlation(self, alpha=None, nlags=5, min_pairs=20, t_first=1):
+        """Are the standardised innovations of DIFFERENT series of a model uncorrelated -- at the same step and at the lags
+        ``1 .. nlags`` in CALENDAR steps?  Under the fitted model they are independent N(0,1) across time and across series;
+        correlation that remains between two series is the signature of a common factor that is missing or has the wrong
+        loadings.  ``e[t,j]`` is CONDITIONED on the series before ``j`` of the same step (the filter's sequential updates), so
+        ``r_ij(0)`` is the correlation left AFTER the model's own account of the two series' common part -- exactly what the
+        test is for.  With ``e~`` the innovations of a series centred and scaled by their own mean and standard deviation,
+        ``n_ij(l)`` the number of steps t at which (t, i) and (t - l, j) are both observed (``t - l >= t_first``) and ``r_ij(l) =
+        sum e~[t,i] e~[t-l,j] / n``: DataFrame indexed by model with ``Q = sum n r^2`` over the pairs ``i < j`` at lag 0 and
+        ``i != j`` at the lags >= 1 that have ``n >= min_pairs``, ``df`` = the number of those terms, ``pvalue = chi2.sf(Q,
+        df)``, and the term of largest ``|z|``, ``z = r sqrt(n)``: ``series_a``, ``series_b``, ``lag``, ``r``, ``z``
+        (``series_a`` at t, ``series_b`` at t - lag).  As in ``test_whiteness`` NO degrees of freedom are subtracted for the
+        estimated parameters: the p-value is on the generous side for a calibrated model.  NaN where no pair has
+        ``min_pairs`` common steps."""
+        from pandas import DataFrame, Index
+
+        from .residuals import cross_correlation
+
+        counts, sums = self._residual_cross(alpha, t_first, nlags)
+        rows = []
+        for r in range(self.R):
+            c = cross_correlation(counts[r], sums[r], min_pairs)
+            w = c["worst"]
+            names = self.batch.names[r]
+            rows.append({"Q": c["Q"], "df": c["df"], "pvalue": c["pvalue"], "series_a": None if w is None else names[w[0]],
+                         "series_b": None if w is None else names[w[1]], "lag": -1 if w is None else w[2],
+                         "r": np.nan if w is None else w[3], "z": np.nan if w is None else w[4]})
+        return DataFrame(rows, index=Index([r + self.shard[0] for r in range(self.R)], name="model"),
+                         columns=["Q", "df", "pvalue", "series_a", "series_b", "lag", "r", "z"])
+
+    def get_residual_correlations(self, r, lag=0, nlags=None, alpha=None, t_first=1):
+        """The ``N x N`` DataFrame of ``r_ij(lag)`` of model ``r`` (``test_cross_correlation``): row ``i`` at step t against
+        column ``j`` at step t - ``lag`` (calendar steps), rows / columns by series name; the diagonal at lag 0 is 1 and at
+        other lags the series' own calendar-lag autocorrelation.  NaN where the two have no common step.  ``nlags``: the
+        number of lags of the device run to read from (default: ``lag``; a run already made for ``test_cross_correlation`` is
+        reused when given the same)."""
+        from pandas import DataFrame
+
+        from .residuals import correlations
+
+        lag = int(lag)
+        nlags = lag if nlags is None else int(nlags)
+        if not 0 <= lag <= nlags:
+            raise ValueError("lag must be in 0..nlags")
+        if not 0 <= int(r) < self.R:
+            raise IndexError("model %d is outside the batch's %d models" % (int(r), self.R))
+        counts, sums = self._residual_cross(alpha, t_first, nlags)
+        names = list(self.batch.names[r])
+        return DataFrame(correlations(counts[r, lag], sums[r, lag]), index=names, columns=names)
+
+    def screen_residuals(self, alpha=None, nlags=10, level=0.01, t_first=1):
+        """The residual checks side by side, one row per (model, series): the p-values ``whiteness`` (``test_whiteness`` with
+        ``nlags``), ``normality`` (``test_normality``), ``heteroskedasticity`` (``test_heteroskedasticity``'s ``H``) and
+        ``cross_correlation`` (``test_cross_correlation`` with ``nlags``; the model's value repeated on its rows), and
+        ``flag``: True where any of them is below ``level``.  A NaN p-value (too few cells) does not flag."""
+        from pandas import DataFrame
+
+        white = self.test_whiteness(alpha, nlags=nlags, t_first=t_first)
+        cross = self.test_cross_correlation(alpha, nlags=nlags, t_first=t_first)["pvalue"].values
+        frame = DataFrame({"whiteness": white["pvalue"].values,
+                           "normality": self.test_normality(alpha, t_first=t_first)["pvalue"].values,
+                           "heteroskedasticity": self.test_heteroskedasticity(alpha, t_first=t_first)["pvalue"].values,
+                           "cross_correlation": np.repeat(cross, self.N)}, index=white.index)
+        with np.errstate(invalid="ignore"):
+            frame["flag"] = (frame.values < float(level)).any(axis=1)
+        return frame
+
     # ------------------------------------------------------------------ multi-step-ahead forecasts and their skill
     def _forecast(self, alpha, outputs, horizon=1, track_horizon=1, t_first=1, coverage=0.95):
         """``BatchedKalman.forecast`` for the parameter set: the cached kind "forecast", one result per REQUEST (outputs,

@@ -18,6 +18,7 @@
 #include "forecast_kernels.h"
 #include "functional_kernels.h"
 #include "innov_kernels.h"
+#include "resid_kernels.h"
 #include "mk_generic.h"
 #include "mk_internal.h"
 #include "mk_lbfgs.h"
@@ -1605,6 +1606,70 @@ MK_API int mk_innovation_stats(mk_context *ctx, int64_t B, int64_t T, int64_t N,
     a.f = d_f;
     a.stats = d_stats;
     MK_HIP(mk::launch_innov_stats(a, ctx->stream));
+    return MK_OK;
+}
+
+// ---- residual diagnostics of the standardised innovations (resid_kernels.hip) ----
+MK_API int mk_residual_series(mk_context *ctx, int64_t B, int64_t T, int64_t N, int time_major, int64_t t_first, const double *d_v,
+                              const double *d_f, double *d_stats)
+{
+    MK_CTX(ctx);
+    if (B < 1 || T < 1 || N < 1 || t_first < 0) return fail(MK_ERR_INVALID, "mk_residual_series: need B, T, N >= 1 and t_first >= 0");
+    if (!d_v) return fail(MK_ERR_INVALID, "mk_residual_series: d_v is required");
+    if (!d_f) return fail(MK_ERR_INVALID, "mk_residual_series: d_f is required");
+    if (!d_stats) return fail(MK_ERR_INVALID, "mk_residual_series: d_stats is required");
+    const device_buffer bufs[3] = {{d_v, B * T * N, "d_v (B * T * N doubles)"},
+                                   {d_f, B * T * N, "d_f (B * T * N doubles)"},
+                                   {d_stats, B * N * mk::resid_stats, "d_stats (B * N * 12 doubles)"}};
+    if (int rc = buffers_fit("mk_residual_series", bufs, 3)) return rc;
+    mk::ResidSeriesArgs a;
+    memset(&a, 0, sizeof(a));
+    a.B = B;
+    a.T = T;
+    a.N = (int)N;
+    fill_layout(a, time_major, B, T);
+    a.t_first = t_first;
+    a.v = d_v;
+    a.f = d_f;
+    a.stats = d_stats;
+    MK_HIP(mk::launch_resid_series(a, ctx->stream));
+    return MK_OK;
+}
+
+MK_API int mk_residual_cross(mk_context *ctx, int64_t B, int64_t T, int64_t N, int time_major, int64_t t_first, int64_t nlags,
+                             const double *d_v, const double *d_f, const double *d_stats, int64_t *d_counts, double *d_sums)
+{
+    MK_CTX(ctx);
+    if (B < 1 || T < 1 || N < 1 || t_first < 0) return fail(MK_ERR_INVALID, "mk_residual_cross: need B, T, N >= 1 and t_first >= 0");
+    if (N > mk::resid_max_series) return fail(MK_ERR_INVALID, "mk_residual_cross: N = %lld, need N <= %d", (long long)N, mk::resid_max_series);
+    if (nlags < 0 || nlags > mk::resid_max_lags)
+        return fail(MK_ERR_INVALID, "mk_residual_cross: nlags = %lld, need 0 <= nlags <= %d", (long long)nlags, mk::resid_max_lags);
+    if (!d_v) return fail(MK_ERR_INVALID, "mk_residual_cross: d_v is required");
+    if (!d_f) return fail(MK_ERR_INVALID, "mk_residual_cross: d_f is required");
+    if (!d_stats) return fail(MK_ERR_INVALID, "mk_residual_cross: d_stats is required (the rows written by mk_residual_series)");
+    if (!d_counts) return fail(MK_ERR_INVALID, "mk_residual_cross: d_counts is required");
+    if (!d_sums) return fail(MK_ERR_INVALID, "mk_residual_cross: d_sums is required");
+    const int64_t pairs = B * (nlags + 1) * N * N;
+    const device_buffer bufs[5] = {{d_v, B * T * N, "d_v (B * T * N doubles)"},
+                                   {d_f, B * T * N, "d_f (B * T * N doubles)"},
+                                   {d_stats, B * N * mk::resid_stats, "d_stats (B * N * 12 doubles)"},
+                                   {d_counts, pairs, "d_counts (B * (nlags + 1) * N * N 64-bit integers)"},
+                                   {d_sums, pairs, "d_sums (B * (nlags + 1) * N * N doubles)"}};
+    if (int rc = buffers_fit("mk_residual_cross", bufs, 5)) return rc;
+    mk::ResidCrossArgs a;
+    memset(&a, 0, sizeof(a));
+    a.B = B;
+    a.T = T;
+    a.N = (int)N;
+    a.L = (int)nlags;
+    fill_layout(a, time_major, B, T);
+    a.t_first = t_first;
+    a.v = d_v;
+    a.f = d_f;
+    a.stats = d_stats;
+    a.counts = (long long *)d_counts;
+    a.sums = d_sums;
+    MK_HIP(mk::launch_resid_cross(a, ctx->stream));
     return MK_OK;
 }
 

@@ -906,6 +906,58 @@ class BatchedKalman:
                                           self._p(stats)))
         return stats
 
+    def _residual_cells(self, v, f, t_first):
+        """The checks ``innovation_stats`` makes of ``v``, ``f`` and ``t_first`` -> ``(B, T, N, t_first)``."""
+        torch = _torch()
+        t_first = int(t_first)
+        if t_first < 0:
+            raise ValueError("t_first must be >= 0")
+        if v.ndim != 3 or tuple(v.shape) != tuple(f.shape):
+            raise ValueError("v and f must be [B,T,N] tensors of one shape")
+        for name, t in (("v", v), ("f", f)):
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.device == self.device and self._layout(t) is t):
+                raise ValueError("%s must be a float64 tensor on %s in the engine's layout" % (name, self.device))
+        B, T, N = (int(s) for s in v.shape)
+        return B, T, N, t_first
+
+    def residual_series(self, v, f, t_first=0):
+        """Moments, variance thirds and CUSUM excursions of the standardised innovations ``e = v / sqrt(f)`` per (instance,
+        series) (C ABI ``mk_residual_series``).  Over the valid cells (finite ``v``, finite ``f > 0``, ``t >= t_first``)
+        ``e_1 .. e_m`` in time order, with ``d_i = e_i - mean``: returns ``[B,N,12]`` = ``[m, mean, S2, S3, S4, h, ss_first,
+        ss_last, cusum, cusum_t, cusq, cusq_t]`` -- ``S_k = sum d_i^k`` (not divided); ``h = (m + 1) // 3`` and the sums of
+        ``e^2`` over the first and the last ``h`` valid cells; ``cusum = max_k |sum_{i<=k} d_i|`` and ``cusq = max_k
+        |sum_{i<=k} d_i^2 - (k / m) S2|``, each with the calendar step of the first ``k`` that attains it.  ``m = 0``: NaN but for
+        ``m = h = 0``.  ``v``, ``f``: ``[B,T,N]`` tensors in the engine's layout (as ``innovations`` returns them)."""
+        torch = _torch()
+        B, T, N, t_first = self._residual_cells(v, f, t_first)
+        stats = torch.empty((B, N, 12), dtype=torch.float64, device=self.device)
+        self._bind_stream()
+        check(self._L.mk_residual_series(self._ctx, B, T, N, 1 if self.time_major else 0, t_first, self._p(v), self._p(f), self._p(stats)))
+        return stats
+
+    def residual_cross(self, v, f, stats, nlags=10, t_first=0):
+        """Lagged sums of products BETWEEN the series of an instance (C ABI ``mk_residual_cross``): with ``e~ = d / sqrt(S2 / m)``
+        from ``stats`` (``residual_series`` of the same ``v``, ``f``, ``t_first``), for the lags ``l = 0 .. nlags`` in CALENDAR
+        steps and all ordered pairs, ``counts[b,l,i,j]`` = the number of steps t at which (t, i) and (t - l, j) are both valid
+        (int64) and ``sums[b,l,i,j] = sum e~[t,i] e~[t-l,j]`` over them, both ``[B,nlags+1,N,N]``; a pair with a series that has no
+        valid cell or does not vary gets 0 and NaN.  ``N <= 64``, ``0 <= nlags <= 32``.  Returns ``(counts, sums)``."""
+        torch = _torch()
+        nlags = int(nlags)
+        if not 0 <= nlags <= 32:
+            raise ValueError("nlags must be in 0..32")
+        B, T, N, t_first = self._residual_cells(v, f, t_first)
+        if N > 64:
+            raise ValueError("residual_cross serves N <= 64 series")
+        if not (isinstance(stats, torch.Tensor) and stats.dtype == torch.float64 and stats.device == self.device
+                and tuple(stats.shape) == (B, N, 12) and stats.is_contiguous()):
+            raise ValueError("stats must be the contiguous float64 [B,N,12] tensor of residual_series on %s" % (self.device,))
+        counts = torch.empty((B, nlags + 1, N, N), dtype=torch.int64, device=self.device)
+        sums = torch.empty((B, nlags + 1, N, N), dtype=torch.float64, device=self.device)
+        self._bind_stream()
+        check(self._L.mk_residual_cross(self._ctx, B, T, N, 1 if self.time_major else 0, t_first, nlags, self._p(v), self._p(f),
+                                        self._p(stats), self._p(counts), self._p(sums)))
+        return counts, sums
+
     # ------------------------------------------------------------------ multi-step-ahead forecasts and forecast skill
     _FORECAST_OUTPUTS = ("fan", "track", "skill")
 
