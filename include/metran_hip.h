@@ -209,7 +209,9 @@ enum { MK_VARIANT_SMOOTHER16 = 0, MK_VARIANT_WIDE_SMOOTHER = 1, MK_VARIANT_WIDE_
 MK_API int mk_set_kernel_variant(mk_context *ctx, int which, int value);
 MK_API int mk_get_kernel_variant(mk_context *ctx, int which, int *value);
 /* Tell the context that the CONTENTS of an observation buffer it has seen changed in place (same pointer): per-record
- * data derived from it (the observed-step list of the sparse objective, see mk_loglik) is rebuilt on the next call.
+ * data derived from it (the observed-step list of the sparse objective, see mk_loglik; which records the record smoother's
+ * rank-K covariance step is taken for, and whether EVERY step of EVERY record is full, in which case mk_smooth /
+ * mk_filter_smooth run a form of the kernel that never looks at the observations) is rebuilt on the next call.
  * Not needed when a different buffer is passed. */
 MK_API int mk_observations_changed(mk_context *ctx);
 /* 1 if the library serves (N,K): a SPECIALISED kernel (compiled ahead of time, or a registered shape module: N + K <= 64,

@@ -40,7 +40,8 @@ struct mk_context {
     // mk_observations_changed() since (the solver evaluates the objective ~80 times on one uploaded record)
     const double *tlist_obs;
     long tlist_T, tlist_N, tlist_ostep;
-    // which records take the record smoother's rank-K covariance step (mk::launch_full_records): device bytes [R] and "any of them",
+    // which records take the record smoother's rank-K covariance step (mk::launch_full_records): device bytes [R] and, in one
+    // word (lr_any: mk::MK_FULL_ANY | mk::MK_FULL_GAP), "any of them" and "some record has a step that is not full",
     // counted once per observation set -- same pointer, shape and layout, and no mk_observations_changed() since
     unsigned char *lr_take;
     long lr_cap;
@@ -910,10 +911,12 @@ static int do_filter(mk_context *ctx, const mk_problem *p, const mk_outputs *o)
 // series.  Counted on the device once per observation set (the count reads every cell; the answer is kept until the pointer, the
 // shape or the layout changes or mk_observations_changed() is called) and read back once, so that a launch in which no record
 // qualifies runs the parent's kernel.  *take = nullptr: do not take the step (also while the stream is being captured and the
-// answer is not there yet: the read-back would need a synchronisation).
-static hipError_t full_records(mk_context *ctx, const mk_problem *p, const unsigned char **take)
+// answer is not there yet: the read-back would need a synchronisation).  *all: every step of every record is full (the second bit of
+// the same word, mk::MK_FULL_GAP, is clear) -- the launch may run the form of the kernel that looks at no observation.
+static hipError_t full_records(mk_context *ctx, const mk_problem *p, const unsigned char **take, long *all)
 {
     *take = nullptr;
+    *all = 0;
     const long bs = p->obs_time_major ? 1 : p->T;
     if (!(ctx->lr_obs == p->d_obs && ctx->lr_R == p->n_records && ctx->lr_T == p->T && ctx->lr_N == p->N && ctx->lr_bs == bs)) {
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -951,7 +954,8 @@ static hipError_t full_records(mk_context *ctx, const mk_problem *p, const unsig
         ctx->lr_N = p->N;
         ctx->lr_bs = bs;
     }
-    if (ctx->lr_any) *take = ctx->lr_take;
+    if (ctx->lr_any & mk::MK_FULL_ANY) *take = ctx->lr_take;
+    *all = ctx->lr_any == mk::MK_FULL_ANY;
     return hipSuccess;
 }
 
@@ -1004,6 +1008,7 @@ static int do_smooth(mk_context *ctx, const mk_problem *p, const mk_outputs *o, 
     // the values behind it.  MK_VARIANT_SMOOTHER16 = 2 keeps the general products at every step
     a.obs = nullptr;
     a.lr_take = nullptr;
+    a.lr_all = 0;
     a.obs_bs = a.obs_ts = 0;
     // (the kernel addresses a cell by a 32-bit byte offset from a base that walks in time: observations below 4 GiB)
     if (p->d_obs && p->d_loadings && !p->d_obsvar && !tape && ctx->variant[MK_VARIANT_SMOOTHER16] != 2 &&
@@ -1011,7 +1016,7 @@ static int do_smooth(mk_context *ctx, const mk_problem *p, const mk_outputs *o, 
         // ... and only for shapes and record forms whose kernel has the step (everything else never looks at the observations)
         const bool served = !sym && !var && o->record_stride && !(o->d_sim_means || o->d_sim_vars) && p->N + p->K <= 10 &&
                             ctx->variant[MK_VARIANT_SMOOTHER16] == 0 && ctx->variant[MK_VARIANT_KERNEL_FAMILY] == 0;
-        if (served) MK_HIP(full_records(ctx, p, &a.lr_take));
+        if (served) MK_HIP(full_records(ctx, p, &a.lr_take, &a.lr_all));
         if (a.lr_take) {
             a.obs = p->d_obs;
             a.obs_bs = p->obs_time_major ? 1 : p->T;

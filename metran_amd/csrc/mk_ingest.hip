@@ -142,6 +142,9 @@ hipError_t launch_pack(long RT, int N, const double *obs, double *observations, 
 // Which records the record smoother's rank-K covariance step is taken for (smoother_record_kernel LR): one
 // 256-thread block per record counts the steps at which every series is observed -- exactly, so the answer does not depend on T
 // or on where a sample would fall -- and sets take[r] where they are at least 7 of 8.  Record (r, t) at row r*obs_bs + t*obs_ts.
+// *any (zeroed by the caller): MK_FULL_ANY where some record qualifies, MK_FULL_GAP where some record has a step that is not
+// full -- so a word of exactly MK_FULL_ANY says that EVERY record observes every series at all T steps (the launch-uniform
+// FULL form of the kernel, which looks at no observation)
 __global__ void __launch_bounds__(256)
 full_records_kernel(long T, int N, long obs_bs, long obs_ts, const double *obs, unsigned char *take, int *any)
 {
@@ -160,7 +163,8 @@ full_records_kernel(long T, int N, long obs_bs, long obs_ts, const double *obs, 
     if (threadIdx.x == 0) {
         const bool ok = 8ull * s_cnt >= 7ull * (unsigned long long)T;
         take[blockIdx.x] = ok ? 1 : 0;
-        if (ok) atomicOr(any, 1);
+        const int word = (ok ? MK_FULL_ANY : 0) | ((unsigned long long)s_cnt != (unsigned long long)T ? MK_FULL_GAP : 0);
+        if (word) atomicOr(any, word);
     }
 }
 

@@ -100,6 +100,8 @@ struct SmootherArgs {
     const double *obs;
     long obs_bs, obs_ts;
     const unsigned char *lr_take; // [R], with obs: 1 where at least 7 of 8 of the record's steps observe every series (full_records_kernel)
+    long lr_all;         // with obs: every record observes every series at all T steps -- the launch-uniform FULL form, which reads neither
+                         // obs nor lr_take
 };
 
 struct AdjointArgs {
@@ -189,7 +191,9 @@ hipError_t launch_standardize(long R, long T, int N, int time_major, const doubl
 hipError_t launch_mask(long count, const double *obs, const unsigned char *mask, double *out, hipStream_t s);
 hipError_t launch_pack(long RT, int N, const double *obs, double *observations, double *indices, long *count,
                        hipStream_t s);
-// take[r] = 1 where at least 7 of 8 of record r's T steps have all N cells finite; *any |= 1 if some record qualifies (zeroed by the caller)
+// take[r] = 1 where at least 7 of 8 of record r's T steps have all N cells finite; *any (zeroed by the caller) |= MK_FULL_ANY if some
+// record qualifies, |= MK_FULL_GAP if some record has a step that is not full: *any == MK_FULL_ANY says every step of every record is full
+constexpr int MK_FULL_ANY = 1, MK_FULL_GAP = 2;
 hipError_t launch_full_records(long R, long T, int N, long obs_bs, long obs_ts, const double *obs, unsigned char *take, int *any,
                                hipStream_t s);
 // mk_factor.hip

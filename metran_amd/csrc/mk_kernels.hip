@@ -1061,9 +1061,15 @@ struct RecordIO {
 // under the EXEC mask of its 16-lane groups -- what a model computes never depends on its neighbours.  A mixed wavefront pays
 // both forms, so a model takes the step only if at least 7 of 8 of ITS record's steps are full (a.lr_take, counted exactly by
 // full_records_kernel once per uploaded observation set); a launch in which no record qualifies runs the parent's kernel.
-template <int N, int K, int G, int EPI, bool SYM, bool LR = false>
+// FULL (with LR; a.lr_all: the same count found EVERY step of EVERY record full): the answer is the launch's, not the step's, so
+// the loop carries no flag at all -- no observation word is fetched, nothing is balloted or masked, no branch surrounds the
+// products and the general ones are not compiled behind it.  Every floating-point operation a model executes is the one it
+// executes in the LR kernel at a full step (the same sweeps on the same operands, the cold pivot redo included).
+template <int N, int K, int G, int EPI, bool SYM, bool LR = false, bool FULL = false>
 __global__ void __launch_bounds__(256) smoother_record_kernel(SmootherArgs a)
 {
+    static_assert(!FULL || LR, "the launch-uniform form is a form of the rank-K step");
+    constexpr bool FLAGS = LR && !FULL; // the per-step "is this step full?" machinery
     constexpr bool PROJ = (EPI == 1), VAR = (EPI == 2);
     constexpr int n = N + K;
     static_assert(n <= G, "state dimension must fit the lane group");
@@ -1143,7 +1149,7 @@ __global__ void __launch_bounds__(256) smoother_record_kernel(SmootherArgs a)
     // synchronisation); the flags are wavefront-uniform lane masks (SGPRs), expanded per lane where the products branch; and
     // the lane index is formed where it is used (lane_now: the empty asm keeps it from being hoisted into a register)
     __shared__ double lds_gam[LR ? 256 * K : 1];
-    __shared__ unsigned lds_ooff[LR ? 256 : 1];
+    __shared__ unsigned lds_ooff[FLAGS ? 256 : 1];
     long otoff = 0, ostepb = 0; // byte offset of the step being fetched (wavefront-uniform), bytes per step
     unsigned ooff = 0;
     int yhi = 0, wbase = 0;
@@ -1155,11 +1161,13 @@ __global__ void __launch_bounds__(256) smoother_record_kernel(SmootherArgs a)
         return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, z));
     };
     if constexpr (LR) {
-        ostepb = a.obs_ts * N * (long)sizeof(double);
-        otoff = (T - 1) * ostepb;
         wbase = __builtin_amdgcn_readfirstlane((int)(threadIdx.x & ~63u));
 #pragma unroll
         for (int k = 0; k < K; ++k) lds_gam[k * 256 + threadIdx.x] = gam[k];
+    }
+    if constexpr (FLAGS) {
+        ostepb = a.obs_ts * N * (long)sizeof(double);
+        otoff = (T - 1) * ostepb;
         const unsigned mbase = (unsigned)(rec_id * a.obs_bs * N * (long)sizeof(double)) + 4u; // high word of the model's cell 0
         lds_ooff[threadIdx.x] = mbase + (unsigned)jr * (unsigned)sizeof(double);
         lr_models = __ballot(a.lr_take[rec_id] != 0); // the model's record is full at 7 of 8 of its steps or more
@@ -1168,16 +1176,16 @@ __global__ void __launch_bounds__(256) smoother_record_kernel(SmootherArgs a)
     auto issue = [&](double &xnext) __attribute__((always_inline)) {
         recF -= rstep;
         RIO::load_issue(recF, rmap, prer);
-        if constexpr (LR) {
+        if constexpr (FLAGS) {
             otoff -= ostepb;
             asm volatile("" : "+s"(otoff)); // stays a scalar: no per-lane pointer is strength-reduced out of the address
             yhi = *reinterpret_cast<const int *>(reinterpret_cast<const char *>(a.obs) + otoff + ooff);
         }
     };
     auto finish = [&](double &xv, double(&row)[n]) __attribute__((always_inline)) {
-        if constexpr (LR) ooff = lds_ooff[wbase + lane_now()]; // for the issue() that follows; rides with the row's LDS reads
+        if constexpr (FLAGS) ooff = lds_ooff[wbase + lane_now()]; // for the issue() that follows; rides with the row's LDS reads
         RIO::load_finish(imgL, prer, rmap, gw, r, xv, row);
-        if constexpr (LR) {
+        if constexpr (FLAGS) {
             unsigned long long m = __ballot((yhi & 0x7ff00000) != 0x7ff00000); // finite cells; all 16 bits of a group: a full step
             m &= m >> 1;
             m &= m >> 2;
@@ -1364,7 +1372,14 @@ __global__ void __launch_bounds__(256) smoother_record_kernel(SmootherArgs a)
         // ---- smoothed covariance (:465-474): Ps[t] = Pf[t] + J (Ps[t+1] - Pp[t+1]) J^T ----
         double V[n]; // V = J D (row r):  V[c] += J[r][k] * D[k][c], D[k][:] broadcast from lane k
         if constexpr (G == 16) dpp_guard(D); // D is compiler-produced (build-time hazard check)
-        if constexpr (LR) {
+        if constexpr (FULL) { // Pf[t] has rank K at every step of every model of the launch
+            double u[K], gl[K];
+            const int ln = lane_now();
+#pragma unroll
+            for (int k = 0; k < K; ++k) gl[k] = lds_gam[k * 256 + wbase + ln];
+            Sweeps<n>::lowrank(u, D, z);
+            Sweeps<n>::lowrank_apply(Psn, u, gl);
+        } else if constexpr (LR) {
             // Pf[t] has rank K where the model observed every series at t: u B^T in place of both products.  The branch is
             // uniform within a model's lane group, so every DPP read stays inside the active lanes
             const int ln = lane_now();
@@ -2625,9 +2640,26 @@ static hipError_t launch_smoother_nk(const SmootherArgs &a, hipStream_t s)
                 }
                 return lowrank > 0 && lowrank >= parent;
             }();
-            if (a.rs > 0 && a.obs && epi == 0 && !a.sym && keeps_occupancy) {
-                hipLaunchKernelGGL((smoother_record_kernel<N, K, G, 0, false, true>), dim3(grid), dim3(256), 0, s, a);
-                return hipGetLastError();
+            // ... and its launch-uniform FULL form where every step of every record of the launch is full (a.lr_all), under the same
+            // rule: a shape at which that form would cost a resident wavefront keeps the kernel it has without it
+            static const bool full_keeps_occupancy = [] {
+                int parent = 0, full = 0;
+                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&parent, smoother_record_kernel<N, K, G, 0, false, false>, 256, 0) != hipSuccess ||
+                    hipOccupancyMaxActiveBlocksPerMultiprocessor(&full, smoother_record_kernel<N, K, G, 0, false, true, true>, 256, 0) != hipSuccess) {
+                    (void)hipGetLastError();
+                    return false;
+                }
+                return full > 0 && full >= parent;
+            }();
+            if (a.rs > 0 && a.obs && epi == 0 && !a.sym) {
+                if (a.lr_all && full_keeps_occupancy) {
+                    hipLaunchKernelGGL((smoother_record_kernel<N, K, G, 0, false, true, true>), dim3(grid), dim3(256), 0, s, a);
+                    return hipGetLastError();
+                }
+                if (keeps_occupancy) {
+                    hipLaunchKernelGGL((smoother_record_kernel<N, K, G, 0, false, true>), dim3(grid), dim3(256), 0, s, a);
+                    return hipGetLastError();
+                }
             }
         }
         if (a.rs > 0) {
