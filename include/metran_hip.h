@@ -782,6 +782,36 @@ MK_API int64_t mk_block_work_stride(int64_t N, int64_t K);
 MK_API int mk_block_predict(mk_context *ctx, const mk_problem *prob, double *d_work, int time_major, const mk_block_request *req,
                             uint32_t *d_status);
 
+/* ---- level-shift scan (shift_kernels.hip) -----------------------------------------------------------------------------------------
+ * For every observed cell (tau, j) the GLS statistic of a LEVEL SHIFT of series j from step tau on, a date that is not known in
+ * advance (mk_regression estimates a shift whose date is given): the regressor x = 1 on the observed cells (t, j) with t >= tau,
+ *     A = x'u,   D = x'Mx:     estimate = A / D,   standard error = 1 / sqrt(D),   t = A / sqrt(D)
+ * with M and u of the leave-block-out predictions above, in the units of the observations the filter runs on (de Jong & Penzer
+ * 1998).  All dates come from ONE backward walk over the gain tape: beside (r, N) it carries per series j the vector Omega_j (the sum
+ * of omega_c over the cells of series j already passed) and the scalars A_j, D_j, all zero behind the last step.  At an observed cell
+ * s = (t, j'), behind step 1 of the walk above:
+ *     m_j = -k_s'Omega_j,   Omega_j <- Omega_j + z_j'' m_j                                   for every series j
+ *     D_j' <- D_j' + M_ss + 2 m_j',   A_j' <- A_j' + u_s,   Omega_j' <- Omega_j' + M_ss z_j'' - g
+ * then step 4; behind the cells of a step, an empty one too, Omega_j <- phi o Omega_j beside the pull-back.  Behind the cells of step
+ * tau, (A_j, D_j) is the pair of the shift of series j that starts at tau.
+ *   mk_shift_work_stride   doubles per (instance, step) of d_work: mk_block_work_stride
+ *   mk_level_shifts        Launches: the recording forward pass into d_work, the clear of the tape, innov_step_kernel writing the tape
+ *                          and v, then shift_scan_kernel (one lane group per instance) -- timed in the smoother slot of
+ *                          mk_last_kernel_ms / mk_kernel_ms_totals.  d_num[b, t, j] = A and d_den[b, t, j] = D where cell (t, j) is
+ *                          observed, NaN where it is not; [B, T, N] addressed by time_major like d_work.  Every sum has a fixed order:
+ *                          an instance's outputs are bit-identical whatever the batch or the layout.  prob->warmup is ignored;
+ *                          d_status (may be NULL) receives the filter's MK_FLAG_* bits -- the outputs of an instance with
+ *                          MK_FLAG_NONPOSITIVE_F are not meaningful.
+ *   Served: every supported shape with N + K <= 64, under either kernel family; otherwise MK_ERR_SHAPE.  MK_ERR_INVALID (no
+ * launch): a missing pointer or a buffer larger than the allocation it points into. */
+typedef struct mk_shift_request {
+    double *d_num;                /* [B, T, N]: A = x'u of the shift of series j from step t on */
+    double *d_den;                /* [B, T, N]: D = x'Mx */
+} mk_shift_request;
+MK_API int64_t mk_shift_work_stride(int64_t N, int64_t K);
+MK_API int mk_level_shifts(mk_context *ctx, const mk_problem *prob, double *d_work, int time_major, const mk_shift_request *req,
+                           uint32_t *d_status);
+
 /* ---- exact window means, changes and contrasts of the smoothed signal (functional_kernels.hip) --------------------------------
  * The posterior mean and variance of LINEAR functionals of the smoothed path, per instance b (record r = b % n_records), window w
  * and contrast c:

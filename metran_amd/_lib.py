@@ -145,6 +145,15 @@ class BlockRequest(Structure):
     ]
 
 
+class ShiftRequest(Structure):
+    """``mk_shift_request`` (include/metran_hip.h)."""
+
+    _fields_ = [
+        ("d_num", c_void_p),
+        ("d_den", c_void_p),
+    ]
+
+
 class FunctionalRequest(Structure):
     """``mk_functional_request`` (include/metran_hip.h)."""
 
@@ -240,6 +249,8 @@ API = {
     "mk_block_max_cells": (c_int64, []),
     "mk_block_work_stride": (c_int64, [c_int64, c_int64]),
     "mk_block_predict": (c_int, [c_void_p, POINTER(Problem), c_void_p, c_int, POINTER(BlockRequest), c_void_p]),
+    "mk_shift_work_stride": (c_int64, [c_int64, c_int64]),
+    "mk_level_shifts": (c_int, [c_void_p, POINTER(Problem), c_void_p, c_int, POINTER(ShiftRequest), c_void_p]),
     "mk_functionals_max_contrasts": (c_int64, []),
     "mk_functionals_work_stride": (c_int64, [c_int64, c_int64]),
     "mk_functionals": (c_int, [c_void_p, POINTER(Problem), c_void_p, c_int, POINTER(FunctionalRequest), c_void_p, c_void_p, c_void_p]),

@@ -24,6 +24,8 @@ number comes from the HIP kernels:
                                  test_parameter_stability)
     functionals              ->  exact window means, changes between periods and contrasts of series, from the smoother's
                                  covariance across time (get_window_means, get_window_mean, get_changes)
+    level_shifts             ->  the t-statistic of a level shift of every series from every date, from one backward pass
+                                 (get_level_shift_statistics, get_level_shift, screen_level_shifts, detect_level_shifts)
     draw_smoothed            ->  posterior draws of series and states (get_simulation_draws, get_state_draws)
     draw_window_statistics   ->  window statistics of the draws, reduced on the device (get_window_statistics)
 
@@ -32,7 +34,7 @@ table (``_KINDS``): ``_cache[kind] = (parameter set, {request: kept result})``. 
 parameter set -- different kinds may hold different ones -- and of that result only the keys its accessors read (the table's
 keep-list: never the forward pass's workspace, the records or the tape, which are hundreds of times the outputs), plus what
 the accessors derive from them once (``("simf", standardized)``, ``("decomp", standardized)``).  The kinds with a request
-(``forecast``, ``weights``, ``regress``, ``functionals``, ``blocks``, ``scores``, ``hessian``) keep every request of their parameter set; another parameter set drops them all.  ``solve``,
+(``forecast``, ``weights``, ``regress``, ``functionals``, ``blocks``, ``scores``, ``hessian``; ``shifts`` has none) keep every request of their parameter set; another parameter set drops them all.  ``solve``,
 ``mask_observations``, ``unmask_observations``, ``adjust_observations`` and ``unadjust_observations`` clear the cache.  So asking for another series, the variances after the
 means, or the decomposition after the simulation does not launch anything.  The draws and their window statistics are not
 cached: an ensemble is the size of the thing it summarises.
@@ -90,6 +92,11 @@ def _functionals(mb, phi, q, request):
 def _blocks(mb, phi, q, request):
     """request = the block table as nested tuples [R][W][3]; original units (the facade's scaling is set)."""
     return mb.kf.block_predict(phi, q, np.asarray(request, dtype=np.int64).reshape(mb.R, -1, 3))
+
+
+def _shifts(mb, phi, q, request):
+    """No request: the scan of every (series, date) of every model, in the standardised units the filter runs on."""
+    return mb.kf.level_shifts(phi, q)
 
 
 def _blocks_that_fit(kf, W, L, budget=None):
@@ -160,6 +167,8 @@ _FIT_KINDS = {
     "functionals": (_functionals, False, ("mean", "var")),
     # leave-block-out predictions of the requested gaps, original units
     "blocks": (_blocks, True, ("means", "vars", "summary", "flags")),
+    # the level-shift scan: A = x'u and D = x'Mx of a shift of every series from every date, standardised units
+    "shifts": (_shifts, False, ("num", "den")),
 }
 # The kinds whose engine call takes the parameter set itself, alpha, not (phi, q): kind -> (engine call (facade, alpha, request),
 # keys of the result that are kept).  The same cache and the same status check, through ``MetranBatch._run``.
@@ -1193,6 +1202,124 @@ class MetranBatch:
                 rows.append((umax, self.batch.index[r][t + int(t_first)], m, -np.expm1(m * np.log1p(-2.0 * norm.cdf(-umax)))))
         return DataFrame(rows, columns=["max_abs_u", "time", "nobs", "pvalue"],
                          index=self._rows(lambda r: ((name,) for name in self._state_columns(r)), ["state"]))
+
+    # ------------------------------------------------------------------ level shifts at an unknown date
+    def get_level_shift_statistics(self, alpha=None, standardized=False):
+        """The GLS statistic of a LEVEL SHIFT of every series from every date (``BatchedKalman.level_shifts``; de Jong & Penzer
+        1998): a dict of tensors ``[R,T,N]`` -- at cell (t, j) ``estimate`` of a permanent offset of series j from step t on,
+        its ``stderr`` and ``t`` = estimate / stderr, parameters held fixed -- what ``fit_interventions`` gives for the single
+        effect ``(model, series, "level", t)``, for all dates from one backward pass.  ``estimate`` and ``stderr`` in the series'
+        ORIGINAL units (the shift times the series' standard deviation; the mean does not enter) or standardised ones; ``t`` is
+        the same in both.  NaN where the cell is not observed.  The first observed cell of a series is the shift of the whole
+        record: the series' mean, not a break (``screen_level_shifts`` leaves it out)."""
+        import torch
+
+        out = self._run("shifts", alpha)
+        key = ("stat", bool(standardized))
+        if key not in out:
+            num, den = out["num"], out["den"]
+            root = torch.sqrt(den)
+            scale = 1.0 if standardized else self._std[:, None, :]
+            out[key] = {"estimate": num / den * scale, "stderr": scale / root, "t": num / root}
+        return dict(out[key])
+
+    def get_level_shift(self, r, name, alpha=None):
+        """The level-shift statistics of series ``name`` of model ``r``: DataFrame on the model's index with ``estimate`` and
+        ``stderr`` (original units) and ``t``; NaN rows where the series is not observed."""
+        from pandas import DataFrame
+
+        j = self._series(r, name)
+        stat = self.get_level_shift_statistics(alpha)
+        L = int(self.batch.lengths[r])
+        return DataFrame({key: stat[key][r, :L, j].cpu().numpy() for key in ("estimate", "stderr", "t")}, index=self.batch.index[r][:L])
+
+    def _shift_candidates(self, t_first, min_segment):
+        """``[R,T,N]`` bool: the observed cells at steps >= t_first with at least ``min_segment`` observed cells of their series
+        before them and at least ``min_segment`` from them on."""
+        seen = np.isfinite(self.kf.obs.cpu().numpy())
+        upto = np.cumsum(seen, axis=1)                     # observed cells of the series at the steps <= t
+        before, from_on = upto - seen, upto[:, -1:, :] - upto + seen
+        cand = seen & (before >= int(min_segment)) & (from_on >= int(min_segment))
+        cand[:, :max(int(t_first), 0)] = False
+        return cand
+
+    def screen_level_shifts(self, alpha=None, t_first=1, min_segment=10):
+        """One row per (model, series): where a level shift fits best.  DataFrame indexed (model, series) with ``max_abs_t`` (the
+        largest level-shift t-statistic in magnitude over the candidate dates), ``time`` (its time stamp), ``estimate`` and
+        ``stderr`` of the shift from there on (original units), ``ncand`` (the number m of candidates searched) and ``pvalue``,
+        the Sidak-corrected two-sided normal p-value of the maximum of m statistics, ``1 - (1 - 2 Phi(-max|t|))^m``.  The
+        correction treats the m statistics as independent; neighbouring ones are positively correlated, so the p-value is on the
+        conservative side.  Candidates are the observed cells of the series at the steps ``t >= t_first`` with at least
+        ``min_segment`` observed cells of that series before them and at least ``min_segment`` from them on: a shift over the
+        whole record is the series' mean, not a break, and one over a handful of cells is an outlier patch.  Rows without
+        candidates carry NaN (``time`` NaT)."""
+        from pandas import DataFrame, NaT
+        from scipy.stats import norm
+
+        stat = {key: value.cpu().numpy() for key, value in self.get_level_shift_statistics(alpha).items()}
+        cand = self._shift_candidates(t_first, min_segment)
+        rows = []
+        for r in range(self.R):
+            for j in range(self.N):
+                steps = np.nonzero(cand[r, :, j] & np.isfinite(stat["t"][r, :, j]))[0]
+                if steps.size == 0:
+                    rows.append((np.nan, NaT, np.nan, np.nan, 0, np.nan))
+                    continue
+                t = int(steps[np.argmax(np.abs(stat["t"][r, steps, j]))])
+                tmax, m = float(abs(stat["t"][r, t, j])), int(steps.size)
+                rows.append((tmax, self.batch.index[r][t], float(stat["estimate"][r, t, j]), float(stat["stderr"][r, t, j]), m,
+                             -np.expm1(m * np.log1p(-2.0 * norm.cdf(-tmax)))))
+        return DataFrame(rows, columns=["max_abs_t", "time", "estimate", "stderr", "ncand", "pvalue"],
+                         index=self._rows(lambda r: ((name,) for name in self.batch.names[r]), ["series"]))
+
+    _INTERVENTION_COLUMNS = ("series", "kind", "start", "end", "n_obs", "estimate", "stderr", "t", "pvalue", "dropped")
+
+    def detect_level_shifts(self, level=0.01, max_shifts=4, alpha=None, t_first=1, min_segment=10):
+        """Find level shifts at unknown dates, one per model and round: the shifts found so far are estimated jointly
+        (``fit_interventions``) and taken out of the records (``adjust_observations``), the adjusted records are scanned
+        (``screen_level_shifts``' candidates), and per model the candidate with the largest |t| over all its series is added when
+        its Sidak p-value over the model's total number of candidates is below ``level``.  Stops when no model adds a shift or
+        after ``max_shifts`` (at most 16: the regression's limit) rounds.  Parameters are held fixed throughout.  Returns
+        ``fit_interventions``' frame of the final set, estimated jointly on the records as they are (empty, with the same
+        columns, if nothing was found).  The records are left unadjusted, bit for bit, also when a step raises; records that are
+        already adjusted when it is called are refused (ValueError): revert them first."""
+        from pandas import DataFrame, MultiIndex
+        from scipy.stats import norm
+
+        max_shifts = int(max_shifts)
+        if not 1 <= max_shifts <= 16:
+            raise ValueError("max_shifts must be in 1..16 (the regression takes 16 effects per model)")
+        if not 0 < float(level) < 1:
+            raise ValueError("level must be between 0 and 1")
+        if self.kf.observations_adjusted:
+            raise ValueError("the records are adjusted: call unadjust_observations first (detect_level_shifts adjusts and reverts them itself)")
+        found = [[] for _ in range(self.R)]            # per model (series, step) in the order found
+        effects = lambda: [(r + self.shard[0], self.batch.names[r][j], "level", int(t)) for r in range(self.R) for j, t in found[r]]  # noqa: E731
+        try:
+            for _ in range(max_shifts):
+                self.unadjust_observations()
+                if any(found):
+                    self.adjust_observations(self.fit_interventions(effects(), alpha=alpha, t_first=t_first))
+                tstat = np.abs(self.get_level_shift_statistics(alpha, standardized=True)["t"].cpu().numpy())
+                cand = self._shift_candidates(t_first, min_segment) & np.isfinite(tstat)
+                added = False
+                for r in range(self.R):
+                    for j, t in found[r]:
+                        cand[r, t, j] = False           # a date already in the model's list is no candidate
+                    m = int(cand[r].sum())
+                    if m == 0:
+                        continue
+                    t, j = np.unravel_index(int(np.argmax(np.where(cand[r], tstat[r], -1.0))), tstat[r].shape)
+                    if -np.expm1(m * np.log1p(-2.0 * norm.cdf(-float(tstat[r, t, j])))) < float(level):
+                        found[r].append((int(j), int(t)))
+                        added = True
+                if not added:
+                    break
+        finally:
+            self.unadjust_observations()
+        if not any(found):
+            return DataFrame(columns=list(self._INTERVENTION_COLUMNS), index=MultiIndex.from_tuples([], names=["model", "effect"]))
+        return self.fit_interventions(effects(), alpha=alpha, t_first=t_first)
 
     # ------------------------------------------------------------------ posterior draws (simulation smoother)
     # The draws and their window statistics go to the engine like the cached kinds (``_launch``) but are not kept: an ensemble is

@@ -13,6 +13,7 @@
 #include <new>
 
 #include "block_kernels.h"
+#include "shift_kernels.h"
 #include "draw_kernels.h"
 #include "ensemble_kernels.h"
 #include "forecast_kernels.h"
@@ -2012,6 +2013,40 @@ MK_API int mk_block_predict(mk_context *ctx, const mk_problem *p, double *d_work
         if (int rc = gain_tape_stage(ctx, p, d_work, w, time_major, d_work + w.innov)) return rc;
         MK_HIP(mk::launch_block_checkpoint(a, ctx->stream));
         MK_HIP(mk::launch_block_walk(a, ctx->stream));
+        return MK_OK;
+    });
+}
+
+// ---- level-shift scan (shift_kernels.hip) ----
+MK_API int64_t mk_shift_work_stride(int64_t N, int64_t K)
+{
+    static_assert(mk::shift_max_states == mk::block_max_states, "the scan runs on the blocks' workspace");
+    return mk_block_work_stride(N, K);
+}
+
+MK_API int mk_level_shifts(mk_context *ctx, const mk_problem *p, double *d_work, int time_major, const mk_shift_request *req,
+                           uint32_t *d_status)
+{
+    if (int rc = reader_preamble(ctx, "mk_level_shifts", "mk_shift_request", p, mk::shift_max_states, req, d_work)) return rc;
+    if (!req->d_num || !req->d_den) return fail(MK_ERR_INVALID, "mk_level_shifts: d_num and d_den are required");
+    if (!p->d_obs || !p->d_loadings) return fail(MK_ERR_INVALID, "d_obs and d_loadings are required");
+    if (!mk_shift_work_stride(p->N, p->K)) return too_many_states("mk_level_shifts", p, mk::shift_max_states);
+    const int64_t B = p->n_instances;
+    const work_layout w = layout_of(WORK_SCORES, p->N, p->K, B, p->T);
+    const device_buffer bufs[3] = {{d_work, B * p->T * w.stride, "d_work (n_instances * T * mk_shift_work_stride(N, K) doubles)"},
+                                   {req->d_num, B * p->T * p->N, "d_num (n_instances * T * N doubles)"},
+                                   {req->d_den, B * p->T * p->N, "d_den (n_instances * T * N doubles)"}};
+    if (int rc = buffers_fit("mk_level_shifts", bufs, 3)) return rc;
+    if (int rc = record_pass(ctx, p, d_work, w.rs, time_major, d_status)) return rc;
+    mk::ShiftArgs a = reader_args<mk::ShiftArgs>(p, d_work, w.rs, time_major); // the scan reads the tape, not the records
+    a.gs = w.gs;
+    a.gain = d_work + w.tape;
+    a.v = d_work + w.innov;
+    a.num = req->d_num;
+    a.den = req->d_den;
+    return timed_launches(ctx, [&]() -> int {
+        if (int rc = gain_tape_stage(ctx, p, d_work, w, time_major, d_work + w.innov)) return rc;
+        MK_HIP(mk::launch_shift_scan(a, ctx->stream));
         return MK_OK;
     });
 }

@@ -14,7 +14,8 @@ import logging
 import numpy as np
 
 from . import _lib
-from ._lib import BlockRequest, ForecastRequest, FunctionalRequest, MetranHipError, Outputs, Problem, RegressionRequest, ScoresRequest, WeightsRequest, check
+from ._lib import (BlockRequest, ForecastRequest, FunctionalRequest, MetranHipError, Outputs, Problem, RegressionRequest, ScoresRequest,
+                   ShiftRequest, WeightsRequest, check)
 
 logger = logging.getLogger(__name__)
 
@@ -709,7 +710,7 @@ class BatchedKalman:
         return res
 
     # ------------------------------------------------------------------ the record readers: one scaffold
-    # loo_predict, disturbances, innovations, forecast, observation_weights, regression, scores, block_predict and functionals (which also runs
+    # loo_predict, disturbances, innovations, forecast, observation_weights, regression, scores, block_predict, level_shifts and functionals (which also runs
     # the smoother) run the recording forward pass into a workspace ("_work") and kernels that read its filtered records.  What a
     # reader keeps to itself is the validation of its request, its shapes and its request struct; the table, _reader_stride,
     # _reader_shapes, _reader_buffers and _reader_call are the rest.
@@ -727,12 +728,14 @@ class BatchedKalman:
         "scores": ("mk_scores_work_stride", False, "the scores", "per-step scores serve shapes with N + K <= 64", "alloc_scores"),
         "blocks": ("mk_block_work_stride", False, "leave-block-out predictions", "leave-block-out predictions serve shapes with N + K <= 64",
                    "alloc_block_predict"),
+        "shifts": ("mk_shift_work_stride", False, "the level-shift scan", "the level-shift scan serves shapes with N + K <= 64",
+                   "alloc_level_shifts"),
         "functionals": ("mk_functionals_work_stride", False, "window functionals", "window functionals serve shapes with N + K <= 64",
                         "alloc_functionals"),
     }
 
     # NOTE: loo_supported() and disturbances_supported() are methods, innovations_supported, forecast_supported,
-    # observation_weights_supported, regression_supported, scores_supported, block_predict_supported and functionals_supported properties -- an
+    # observation_weights_supported, regression_supported, scores_supported, block_predict_supported, level_shifts_supported and functionals_supported properties -- an
     # inconsistency of the public API that is kept.
     def _reader_stride(self, name, refuse=False):
         """Doubles per (instance, step) of the workspace of the record reader ``name``; where the engine is not served 0, or with
@@ -1280,6 +1283,38 @@ class BatchedKalman:
             setattr(req, "d_" + key, res[key].data_ptr())
         return self._reader_call("mk_block_predict", prob, res, ctypes.byref(req), mask=("means", "vars", "summary"))
 
+    # ------------------------------------------------------------------ level-shift scan
+    @property
+    def level_shifts_supported(self):
+        """True when ``level_shifts`` serves this engine (C ABI ``mk_shift_work_stride`` > 0): N + K <= 64, specialised or
+        size-generic kernels alike, full-square records."""
+        return self._reader_stride("shifts") > 0
+
+    def _shift_shapes(self, B):
+        return self._reader_shapes(B, bt=dict(num=self.N, den=self.N))
+
+    def alloc_level_shifts(self, B):
+        """Buffers of ``level_shifts`` for B instances (the forward pass's workspace with the gain tape and the innovations + the
+        two outputs), for callers that run it repeatedly (pass them back as ``buffers=``)."""
+        return self._reader_buffers("shifts", None, self._shift_shapes(B))
+
+    def level_shifts(self, phi, q, x0=None, P0=None, buffers=None):
+        """LEVEL-SHIFT SCAN for B instances (C ABI ``mk_level_shifts``): for every observed cell (t, j) the GLS statistic of a
+        permanent offset of series j from step t on -- the regressor x = 1 on the observed cells of series j at the steps >= t --
+        for all dates from one backward walk (de Jong & Penzer 1998).  Returns a dict with ``num [B,T,N]`` = A = x'u,
+        ``den [B,T,N]`` = D = x'Mx (M the precision of the record's data vector, u = M (y - mu)) and ``status`` (the filter's
+        MK_FLAG_* bits): the estimate of the shift is A / D, its standard error 1 / sqrt(D), its t-statistic A / sqrt(D), in the
+        standardised units the filter runs on (``set_scaling`` does not enter); what ``regression`` gives for the single level
+        effect ``(j, level, t, T)`` as ``beta``, ``cov`` and ``gain`` = A^2 / D.  NaN where a cell is not observed; the rows of an
+        instance whose status carries ``FLAG_NONPOSITIVE_F`` are NaN.  Four launches (the recording forward pass, a clear, the
+        gain writer, the scan); an instance's outputs do not depend on the batch or the layout, bit for bit."""
+        stride = self._reader_stride("shifts", refuse=True)
+        prob, keep, B = self._problem(phi, q, 0, x0, P0)
+        res = self._reader_buffers("shifts", buffers, self._shift_shapes(B), stride)
+        req = ShiftRequest()
+        req.d_num, req.d_den = res["num"].data_ptr(), res["den"].data_ptr()
+        return self._reader_call("mk_level_shifts", prob, res, ctypes.byref(req), mask=("num", "den"))
+
     # ------------------------------------------------------------------ exact window means, changes and contrasts
     @property
     def functionals_supported(self):
@@ -1370,6 +1405,11 @@ class BatchedKalman:
         self._grad_pending = self._grad_alpha = None  # a pending forward pass belongs to the records before
         check(self._L.mk_observations_changed(self._ctx))
         return self
+
+    @property
+    def observations_adjusted(self):
+        """True between ``adjust_observations`` and ``unadjust_observations``: the observations carry fitted effects."""
+        return getattr(self, "_obs_unadjusted", None) is not None
 
     def unadjust_observations(self):
         """The observations as they were before ``adjust_observations`` (and the kept unmasked copy, if a mask was active)."""
